@@ -1,6 +1,11 @@
 """Benchmark of the SuperPoint + LightGlue train-step hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up the headline step, runs W warm-up and K timed steps and prints the JSON line (metric, value, unit,
+ms_per_step, ...).  ``--full`` adds every other measurement listed below (``matcher_step`` and the rest); the ``--no-*``
+options leave single ones out of a full run.  ``--dump-outputs DIR`` writes what the timed step returned in its last
+step (``snapshot_outputs``) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 
 ``--gpus N`` with N > 1 and no torchrun environment self-spawns N ranks (one process per GPU, RCCL) through
 ``python -m torch.distributed.run`` on 127.0.0.1, the way gluefactory/train.py:727-734 spawns its workers;
@@ -12,7 +17,7 @@ kernels; library convolutions + fused HIP tails for the 128/256-channel blocks) 
 (gf_gt_nn) -> one full LightGlue train step
 (forward, loss, backward, fused Adam) at B=32 pairs per GPU, N=2048 keypoints, d=256, L=9, bf16 compute.
 Data parallel over N GPUs is weak scaling (32 pairs per GPU) with DDP/RCCL gradient all-reduce.
-Rank 0 prints ONE JSON line (contract in the task statement) that also carries
+Rank 0 prints ONE JSON line that, with ``--full``, also carries
   "matcher_step":  the matcher-only scope (M): the same train step on keypoint pairs already resident in HBM
                    (the reference's cached-feature training mode) -- the scope the roofline fractions refer to;
   "roofline":      the dominant MFMA kernel (attention backward) timed live with HIP events on its stream vs
@@ -89,6 +94,11 @@ def parse():
     ap.add_argument("--no-graph", action="store_true", help="launch the step kernel by kernel instead of replaying a hipGraph")
     ap.add_argument("--matcher-only", action="store_true", help="skip the extractor: scope M becomes the only line")
     ap.add_argument("--dp-graph", action="store_true", help="(accepted for compatibility; N > 1 always measures kernel-by-kernel first and then tries the captured step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the matcher-only step, extractor time, rooflines, "
+                         "PCIe-inclusive step, other configs, CPU baseline (the --no-* options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed step returned in its last step as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -491,7 +501,7 @@ def cpu_baseline(n, layers):
             params = lgo.init_params(ll, DIM, HEADS, seed=0)
             data = make_pairs(1, nn_, dim=DIM, seed=1)
             data = dict(data, image_size0=data["view0"]["image_size"], image_size1=data["view1"]["image_size"])
-            leaves = {k: v.clone().requires_grad_(True) for k, v in params.items()}
+            leaves = {k: params[k].clone().requires_grad_(True) for k in lgo.trainable_names(params)}
             opt = torch.optim.Adam(list(leaves.values()), lr=1e-4)
 
             def step():
@@ -591,11 +601,12 @@ def scope_p_inputs(batch, rank):
             "H_0to1": H.float()}
 
 
-def make_pipeline_step(args, rank, local, graph=True):
+def make_pipeline_step(args, rank, local, graph=True, last=None):
     """Scope P through the product API: ``glue_factory_amd.pipeline.TwoViewPipeline`` (frozen SuperPoint-open extractor ->
     homography ground truth -> LightGlue) inside ``TrainStep`` -- forward, ground truth, loss, backward and the fused Adam
     update of one step, captured as ONE hipGraph (the extractor's top-k is csrc/topk.hip: a captured extractor tail
-    with torch.topk in it faults on its second replay).  Inputs: 2 x batch synthetic IMG x IMG images resident in HBM."""
+    with torch.topk in it faults on its second replay).  Inputs: 2 x batch synthetic IMG x IMG images resident in HBM.
+    ``last``: a dict whose "out" each step sets to the loss dict TrainStep returned."""
     from glue_factory_amd.pipeline import TwoViewPipeline
     torch.manual_seed(0)
     pipe = TwoViewPipeline({
@@ -614,7 +625,10 @@ def make_pipeline_step(args, rank, local, graph=True):
             return pipe.extractor({"image": images})
 
     def pipeline_step():
-        out = stepper(state["data"])["total"].mean()
+        res = stepper(state["data"])
+        if last is not None:
+            last["out"] = res
+        out = res["total"].mean()
         static = stepper.static_inputs()
         if static is not None and state["data"] is not static:
             state["data"] = static        # the graph's own input buffers (same values): no per-step copy of the images
@@ -646,6 +660,34 @@ def timed_steps(step, warmup, steps, barrier, dist):
     if ops.LIBRARY_GEMMS:
         raise SystemExit(f"bench.py: products left the HIP path for the vendor library during a timed configuration: {ops.LIBRARY_GEMMS}")
     return dt, float(loss.item())
+
+
+DUMP_PARAMS = 1 << 20        # parameters sampled for --dump-outputs (4 MB of float32)
+
+
+def snapshot_outputs(out, model):
+    """--dump-outputs: what the timed step hands its caller, copied to the host as name -> float32 / float64 array.
+    `loss.<key>`: the per-sample losses TrainStep returns; `params`: the trainable parameters the step's optimiser update
+    left behind, concatenated in `named_parameters` order, at DUMP_PARAMS positions drawn once with a fixed seed (all of
+    them when there are fewer)."""
+    import numpy as np
+    arrays = {}
+    for k, v in out.items():
+        a = v.detach().cpu()
+        arrays[f"loss.{k}"] = (a.double() if a.dtype == torch.float64 else a.float()).numpy()
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for _, p in model.named_parameters() if p.requires_grad]).cpu().numpy()
+    if flat.size > DUMP_PARAMS:
+        flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, DUMP_PARAMS, replace=False))]
+    arrays["params"] = flat
+    return arrays
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def pcie_inclusive(args, p_stepper, data):
@@ -790,6 +832,7 @@ def data_parallel_report(dist, rank, world, stepper):
 DP_GRAPH_TIMEOUT_S = 240.0
 PRIME_STEPS = 3          # TrainStep(graph=True) runs two eager steps and captures on the third: all three belong to the set-up, so that
                          # `--warmup W` with W < 3 cannot push the capture into the timed region
+WATCHDOG_DRAIN_S = 0.5   # several ranks: pause before the capturing call (the process group's watchdog polls every 100 ms; see prime)
 
 
 class _Watchdog:
@@ -840,7 +883,7 @@ def build_line(args, world, matcher, pipe_res, dp_info, dp_modes, pairs):
                                + ("replayed as ONE hipGraph" if p_stepper.graph else "launched kernel by kernel"),
                    "pairs_per_gpu": args.batch, "global_batch": args.batch * world, "keypoints": args.kpts,
                    "descriptor_dim": DIM, "layers": args.layers, "image_size": [IMG, IMG], "parallelism": f"dp{world}"},
-        "final_loss": round(p_loss, 4), "matcher_step": matcher, **extra}
+        "final_loss": round(p_loss, 4), **({"matcher_step": matcher} if matcher is not None else {}), **extra}
 
 
 def self_spawn(args):
@@ -891,9 +934,13 @@ def main():
                 dist.barrier()
         torch.cuda.synchronize()
 
-    model, cpu_data = build_matcher(args, rank, args.model)
-    data = to_device(cpu_data, "cuda")
     headline_is_pipeline = args.model == "lightglue" and not args.matcher_only
+    # the matcher step on resident keypoint pairs (scope M) is the headline only without the extractor; beside scope P it is
+    # one of the --full measurements
+    time_matcher = args.full or not headline_is_pipeline
+    if time_matcher:
+        model, cpu_data = build_matcher(args, rank, args.model)
+        data = to_device(cpu_data, "cuda")
     pairs = args.batch * world * args.steps
 
     def matcher_entry(m_dt, m_loss, graphed):
@@ -906,24 +953,48 @@ def main():
                                         / world / (MFMA_BF16_PEAK_TFLOPS * 1e12), 4),
                 "final_loss": round(m_loss, 4)}
 
+    def prime(step, stepper):
+        """The PRIME_STEPS set-up calls.  Several ranks with a captured step: the process group's watchdog thread polls the
+        events of the eager steps' collectives until it retires them, and a poll of an event last recorded on a stream that is
+        being captured ends the process (hipErrorCapturedEvent) -- so the eager work is finished and retired first."""
+        for i in range(PRIME_STEPS):
+            if dist is not None and stepper.graph and i == stepper.graph_warmup:
+                torch.cuda.synchronize()
+                time.sleep(WATCHDOG_DRAIN_S)
+            step()
+
+    def snapshot(last, stepper):
+        return snapshot_outputs(last["out"], stepper.model) if args.dump_outputs and rank == 0 else None
+
     def measure(graph):
-        """(matcher entry, pipeline (dt, loss, stepper, extract) or None, data-parallel report or None) with every step
-        either launched kernel by kernel or replayed as one hipGraph."""
-        stepper = make_stepper(args, model, local, allow_graph=graph)
-        for _ in range(PRIME_STEPS):                  # set-up, not warm-up: two eager steps, then the capture of the hipGraph
-            stepper(data)
-        m_dt, m_loss = timed_steps(lambda: stepper(data)["total"].mean(), args.warmup, args.steps, barrier, dist)
-        m = matcher_entry(m_dt, m_loss, stepper.graph)
-        dp = data_parallel_report(dist, rank, world, stepper) if dist is not None else None
-        if not headline_is_pipeline:
-            stepper.close()
-            return m, None, dp
-        pipeline_step, extract, p_stepper = make_pipeline_step(args, rank, local, graph=graph)
-        for _ in range(PRIME_STEPS):                  # MIOpen's convolution search and the graph capture happen here, outside any timing
-            pipeline_step()
+        """(matcher entry or None, pipeline (dt, loss, stepper, extract) or None, data-parallel report or None, the headline
+        step's outputs for --dump-outputs or None) with every step either launched kernel by kernel or replayed as one hipGraph."""
+        m = dp = stepper = None
+        if time_matcher:
+            stepper = make_stepper(args, model, local, allow_graph=graph)
+            prime(lambda: stepper(data), stepper)      # set-up, not warm-up: two eager steps, then the capture of the hipGraph
+            m_last = {}
+
+            def matcher_step():
+                m_last["out"] = stepper(data)
+                return m_last["out"]["total"].mean()
+            m_dt, m_loss = timed_steps(matcher_step, args.warmup, args.steps, barrier, dist)
+            m = matcher_entry(m_dt, m_loss, stepper.graph)
+            dp = data_parallel_report(dist, rank, world, stepper) if dist is not None else None
+            if not headline_is_pipeline:
+                outputs = snapshot(m_last, stepper)
+                stepper.close()
+                return m, None, dp, outputs
+        last = {}
+        pipeline_step, extract, p_stepper = make_pipeline_step(args, rank, local, graph=graph, last=last)
+        prime(pipeline_step, p_stepper)               # MIOpen's convolution search and the graph capture happen here, outside any timing
         p_dt, p_loss = timed_steps(pipeline_step, args.warmup, args.steps, barrier, dist)
-        stepper.close()
-        return m, (p_dt, p_loss, p_stepper, extract), dp
+        outputs = snapshot(last, p_stepper)
+        if stepper is not None:
+            stepper.close()
+        elif dist is not None:
+            dp = data_parallel_report(dist, rank, world, p_stepper)
+        return m, (p_dt, p_loss, p_stepper, extract), dp, outputs
 
     # ---- N = 1: the step is ONE hipGraph.  N > 1: kernel by kernel first (plain torch.distributed calls from autograd
     # hooks: the path the CPU / single-GPU multi-process tests cover), then -- RCCL only -- the CAPTURED bucket-reducer step
@@ -931,18 +1002,22 @@ def main():
     # it hangs (a collective inside a capture that one rank abandoned), every rank prints / exits on the eager numbers after
     # DP_GRAPH_TIMEOUT_S instead of hanging the job.  When both work the line carries both and `value` is the better one.
     dp_modes = None
+
+    def mode_entry(m, p):
+        return {**({"matcher_ms_per_step": m["ms_per_step"]} if m else {}),
+                **({"pipeline_ms_per_step": round(p[0] / args.steps * 1e3, 3)} if p else {})}
+
     if dist is None:
-        matcher, pipe_res, dp_info = measure(graph=True)
+        matcher, pipe_res, dp_info, outputs = measure(graph=True)
     else:
-        matcher, pipe_res, dp_info = measure(graph=False)
-        dp_modes = {"eager": {"matcher_ms_per_step": matcher["ms_per_step"],
-                              **({"pipeline_ms_per_step": round(pipe_res[0] / args.steps * 1e3, 3)} if pipe_res else {})}}
+        matcher, pipe_res, dp_info, outputs = measure(graph=False)
+        dp_modes = {"eager": mode_entry(matcher, pipe_res)}
         try_graph = dist.get_backend() == "nccl" and not args.no_graph
         if try_graph:
             eager_line = build_line(args, world, matcher, pipe_res, dp_info, dict(dp_modes, graph={"status": "timed out"}), pairs)
             dog = _Watchdog(DP_GRAPH_TIMEOUT_S, eager_line if rank == 0 else None)
             try:
-                g_matcher, g_pipe, _ = measure(graph=True)
+                g_matcher, g_pipe, _, g_outputs = measure(graph=True)
                 ok = torch.ones((), device="cuda")
             except Exception as e:          # capture / replay error on this rank
                 g_matcher = g_pipe = None
@@ -952,18 +1027,19 @@ def main():
             torch.cuda.synchronize()
             dog.cancel()
             if float(ok.item()) > 0:
-                dp_modes["graph"] = {"status": "ok", "matcher_ms_per_step": g_matcher["ms_per_step"],
-                                     **({"pipeline_ms_per_step": round(g_pipe[0] / args.steps * 1e3, 3)} if g_pipe else {})}
+                dp_modes["graph"] = {"status": "ok", **mode_entry(g_matcher, g_pipe)}
                 better = (g_pipe[0] < pipe_res[0]) if pipe_res else (g_matcher["ms_per_step"] < matcher["ms_per_step"])
                 if better:
-                    matcher, pipe_res = g_matcher, g_pipe
+                    matcher, pipe_res, outputs = g_matcher, g_pipe, g_outputs
             else:
                 dp_modes.setdefault("graph", {"status": "failed on another rank"})
         else:
             dp_modes["graph"] = {"status": "not attempted (" + ("--no-graph" if args.no_graph else
                                                                f"{dist.get_backend()}: collectives are capturable on RCCL only") + ")"}
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     out = build_line(args, world, matcher, pipe_res, dp_info, dp_modes, pairs)
-    if not headline_is_pipeline:
+    if not headline_is_pipeline or not args.full:
         if rank == 0:
             print(json.dumps(out), flush=True)
         if dist is not None:

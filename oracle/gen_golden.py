@@ -679,6 +679,20 @@ def gen_metrics(name, seed):
     print(name, {k: v.tolist() for k, v in matcher_metrics(pred, data).items()})
 
 
+def gen_metrics_sweep(name):
+    """matcher_metrics of the reference on every case of tests/test_reference_metrics_sweep.py (inputs rebuilt there from
+    their seeds; only the outputs are stored, as "<case>.<metric>")."""
+    from gluefactory.models.utils.metrics import matcher_metrics
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_reference_metrics_sweep as sweep
+    out = {}
+    for case in sweep.CASES:
+        pred, data = sweep.case_inputs(*case)
+        out.update(_np(matcher_metrics(pred, data, prefix=case[4], prefix_gt=case[5]), sweep.case_key(*case) + "."))
+    np.savez_compressed(os.path.join(GOLD, name + ".npz"), **out)
+    print(name, len(sweep.CASES), "cases")
+
+
 def gen_lightglue_adaptive(name, n0, n1, n_layers, seed):
     """Eval-only adaptive depth / width (lightglue.py:461-529, b == 1) of the REFERENCE on seeded weights whose
     token-confidence / matchability biases are shifted so that the stop and the pruning actually trigger."""
@@ -794,6 +808,7 @@ def main():
             "superpoint_options": lambda: gen_superpoint_options("superpoint_options", seed=57),
             "superpoint_nonfree": lambda: gen_superpoint_nonfree("superpoint_nonfree", seed=53),
             "metrics": lambda: gen_metrics("metrics", seed=109),
+            "metrics_sweep": lambda: gen_metrics_sweep("metrics_sweep"),
             "superglue_config4": lambda: gen_superglue_config("superglue_config4", 1, 2048, 100, seed=113),
             "gluestick_config5": lambda: gen_gluestick_config("gluestick_config5", 1, 2048, 512, seed=127),
             "matcher_options": lambda: gen_matcher_options(),
@@ -830,6 +845,7 @@ def main():
     gen_lightglue_config("lightglue_sharp", 1, 2048, 9, seed=131, size=(1024, 1024), stride=997, sharp=(0.04, 11.0, 0.06))
     gen_lightglue_adaptive("lightglue_adaptive", 160, 200, 3, seed=107)
     gen_metrics("metrics", seed=109)
+    gen_metrics_sweep("metrics_sweep")
     gen_superglue_config("superglue_config4", 1, 2048, 100, seed=113)
     gen_gluestick_config("gluestick_config5", 1, 2048, 512, seed=127)
     gen_gluestick("gluestick_lineattn", batch=2, n_kpts=36, n_lines=14, gnn=["self", "cross"] * 2, inter=[0], seed=43,

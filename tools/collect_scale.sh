@@ -18,10 +18,10 @@ export TMPDIR=/tmp
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 for k in 1 2 4 $N; do
   [ "$k" -gt "$N" ] && continue
-  python bench.py --gpus $k --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-other-configs > "$OUT/n$k.json" 2> "$OUT/n$k.err" || echo "n=$k failed"
+  python bench.py --full --gpus $k --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-other-configs > "$OUT/n$k.json" 2> "$OUT/n$k.err" || echo "n=$k failed"
 done
 # N = 1 through the launcher must be the single-process number (same code path, no collective): within 2 %
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-other-configs > "$OUT/single.json" 2> "$OUT/single.err" || echo "single-process run failed"
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-other-configs > "$OUT/single.json" 2> "$OUT/single.err" || echo "single-process run failed"
 python - "$OUT" <<'PY'
 import json, sys
 out = sys.argv[1]

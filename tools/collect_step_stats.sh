@@ -12,7 +12,7 @@ mkdir -p "$OUT" "$REPO/profiles"
 export TMPDIR=/tmp
 EXTRA=""
 [ "$MODEL" != lightglue ] && EXTRA="--model $MODEL"
-CMD="python $REPO/bench.py --steps 15 --warmup 3 --no-graph --no-roofline --no-other-configs --no-cpu-baseline $EXTRA"
+CMD="python $REPO/bench.py --full --steps 15 --warmup 3 --no-graph --no-roofline --no-other-configs --no-cpu-baseline $EXTRA"
 cd /tmp
 timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o stats --output-format csv -- $CMD > "$OUT/stats.log" 2>&1 || echo "stats pass failed"
 cd "$REPO"
