@@ -353,6 +353,8 @@ extern "C" int gf_conv3x3_c64_ld(const void* x, const void* w, const float* bias
     if (H % C3_TH || W % C3_TW) return GF_ERR_UNSUPPORTED;
     if ((int64_t)H * W * 128 >= (1ll << 31)) return GF_ERR_UNSUPPORTED;      // 32-bit byte offsets inside one image (buffer loads)
     if (ldy < 64 || ldy % 8) return GF_ERR_ALIGN;                            // whole 16-byte chunks of a pixel
+    // 16-byte loads of x (LDS-DMA pieces) and w (weight fragments), 16-byte stores through y
+    if ((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(w) | reinterpret_cast<size_t>(y)) & 15) return GF_ERR_ALIGN;
     if ((int64_t)H * W * ldy >= (1ll << 31)) return GF_ERR_UNSUPPORTED;      // (32-bit element offsets inside one output image)
     C3Params p;
     p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(w); p.bias = bias; p.scale = scale; p.shift = shift;

@@ -417,11 +417,13 @@ int gf_conv1_bias_act_bn(const void* img, const void* w, const float* bias, cons
 /* gf_conv3x3_c64: one 64 -> 64 channel VGG block (superpoint_open.py:37-75 VGGBlock, :98-105 backbone.0.1 / 1.0 / 1.1:
  *   Conv2d(64, 64, 3, padding=1) -> +bias -> ReLU -> BatchNorm2d(eval) [-> MaxPool2d(2, 2)]) as one implicit-GEMM
  *   kernel.  x [B,H,W,64] channels-last bf16, w [9 taps (ky*3+kx)][64 c_out][64 c_in] bf16, y [B,H,W,64] or, with
- *   pool != 0, [B,H/2,W/2,64].  dtype must be GF_BF16 (GF_ERR_DTYPE), H % 8 == 0 and W % 32 == 0
- *   (GF_ERR_UNSUPPORTED: the caller uses the library convolution + gf_bias_act_bn_nhwc). */
+ *   pool != 0, [B,H/2,W/2,64].  dtype must be GF_BF16 (GF_ERR_DTYPE), H % 8 == 0, W % 32 == 0 and
+ *   H * W * 128 < 2^31 (GF_ERR_UNSUPPORTED: the caller uses the library convolution + gf_bias_act_bn_nhwc); x, w and y
+ *   16-byte aligned (GF_ERR_ALIGN). */
 int gf_conv3x3_c64(const void* x, const void* w, const float* bias, const float* scale, const float* shift, void* y,
                    int B, int H, int W, int relu, int pool, int dtype, void* stream);
-/* gf_conv3x3_c64_ld (ABI 17): the same with the output's pixel stride ldy (elements, >= 64, % 8 == 0) as an argument: the kernel
+/* gf_conv3x3_c64_ld (ABI 17): the same with the output's pixel stride ldy (elements, >= 64, % 8 == 0; x, w and y 16-byte
+ *   aligned, else GF_ERR_ALIGN) as an argument: the kernel
  *   writes the 64 channels of each pixel into a slice of a WIDER channels-last tensor -- a 64 -> 128 block (backbone.2.0,
  *   superpoint_open.py:101-103) is two calls, one per half of the output channels (w / bias / scale / shift of that half,
  *   y + 64 * half), tail fused, instead of the library convolution + a tail pass. */

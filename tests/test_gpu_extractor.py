@@ -251,6 +251,20 @@ def test_conv3x3_c64_rejects():
                               1, 8, 32, 1, 0, 0, None) == -4          # fp32: GF_ERR_DTYPE
     assert lib.gf_conv3x3_c64(z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(),
                               1, 12, 32, 1, 0, 1, None) == -1         # H % 8: GF_ERR_UNSUPPORTED
+    # misaligned x / w / y (the kernel loads and stores 16-byte chunks through them): GF_ERR_ALIGN, nothing launched
+    x = torch.zeros(8 * 32 * 64 + 64, dtype=torch.bfloat16, device="cuda")
+    y = torch.full((8 * 32 * 128 + 64,), 777.0, dtype=torch.bfloat16, device="cuda")
+    w = torch.zeros(9 * 64 * 64 + 64, dtype=torch.bfloat16, device="cuda")
+    c = torch.zeros(64, device="cuda")
+    args = lambda xo, wo, yo: (x.data_ptr() + xo, w.data_ptr() + wo, c.data_ptr(), c.data_ptr(), c.data_ptr(),  # noqa: E731
+                               y.data_ptr() + yo, 128, 1, 8, 32, 1, 0, 1, None)
+    assert lib.gf_conv3x3_c64_ld(*args(0, 0, 8)) == -3                # y + 4 elements (8 bytes)
+    assert lib.gf_conv3x3_c64_ld(*args(8, 0, 0)) == -3                # x + 8 bytes
+    assert lib.gf_conv3x3_c64_ld(*args(0, 8, 0)) == -3                # w + 8 bytes
+    assert lib.gf_conv3x3_c64(*args(0, 0, 8)[:6], 1, 8, 32, 1, 0, 1, None) == -3
+    assert lib.gf_conv3x3_c64_ld(*args(0, 0, 128)) == 0               # the upper half of a 128-channel output: accepted
+    px = y[:8 * 32 * 128].view(8 * 32, 128)
+    assert bool((px[:, 64:] == 0).all()) and bool((px[:, :64] == 777.0).all())     # (zero weights: upper half 0, lower untouched)
 
 
 @pytest.mark.parametrize("B,n,K,valid_frac", [(3, 87040, 2048, 0.25), (2, 5000, 2048, 0.1), (4, 4096, 4096, 0.6),
