@@ -11,7 +11,7 @@ namespace {
 // ===========================================================================================
 // bf16 forward, third generation: the softmax costs 2.5 VALU instructions per score instead of 5
 // ===========================================================================================
-// The second-generation kernel (attention.hip) is VALU-issue-bound (10 VALU per MFMA;
+// The second-generation kernel (since retired) was VALU-issue-bound (10 VALU per MFMA;
 // `profiles/r02b_attention_sq_counters.txt`).  Per score it spent: max, fma (scale and subtract the running max), exp2,
 // row-sum add, half a cvt_pk.  Here
 //   * Q is pre-multiplied by the POWER-OF-TWO part of scale*log2(e) once per kernel (exact in bf16; pre-multiplying by

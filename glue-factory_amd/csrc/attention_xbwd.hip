@@ -18,7 +18,7 @@
 // splat.
 // One wave = 32 owner tokens, 4 waves per workgroup, ONE workgroup per CU (the five products need ~300 registers: one wave
 // per SIMD, up to 512 unified registers); streamed tiles of 64 tokens x {qk, dO, v} + statistics arrive by
-// `global_load ... lds` in a 3-stage ring (attention.hip: chunk swizzle, ds_read_b128 row reads, ds_read_b64_tr_b16
+// `global_load ... lds` in a 3-stage ring (attn_common.h: chunk swizzle, ds_read_b128 row reads, ds_read_b64_tr_b16
 // transposed reads).
 #include "gf_common.h"
 #include "gf_amd.h"

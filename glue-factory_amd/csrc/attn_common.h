@@ -1,6 +1,6 @@
-// Shared pieces of the attention kernels (attention.hip, attention_fwd3.hip): launch parameters, the row store of a
-// transposed accumulator and the bf16 LDS-DMA / transposing-read helpers.  Everything is static / in a named namespace
-// so that both translation units can include it.
+// Shared pieces of the attention translation units (attention*.hip, head_bwd.hip): launch parameters, the launch functions
+// attention.hip dispatches to, the row store of a transposed accumulator and the bf16 LDS-DMA / transposing-read helpers.
+// Everything is static / in a named namespace so that every translation unit can include it.
 #pragma once
 #include "gf_common.h"
 #include <cmath>
@@ -8,6 +8,9 @@
 namespace gfattn {
 
 enum { GF_ATTN_ACC_DQ = 1, GF_ATTN_ACC_DK = 2 };      // (+ GF_ATTN_SPLIT = 4, include/gf_amd.h)
+// internal flag, set by launch_bwd_generic for the generic dQ kernel: it is paired with the GENERIC dK/dV kernel, which
+// reads lse and delta as they are (without it a bf16 dQ kernel writes what attn_bwd_dkv_bf16_kernel starts from)
+constexpr int ATTN_PLAIN_STATS = 0x100;
 
 struct AttnParams {
     const void* q; const void* k; const void* v; void* o;
@@ -138,7 +141,7 @@ __device__ __forceinline__ void mma16(f32x16& acc, bf16x8 a, bf16x8 b) {
 }
 
 // ===========================================================================================
-// bf16 forward and dQ on the same staging scheme as the dK/dV kernel above
+// bf16 forward and dQ on the same staging scheme as the dK/dV kernel (attention_dkv.hip)
 // ===========================================================================================
 // K and V tiles (64 keys x 128 B, row-major, chunk-swizzled by fswz) arrive by LDS-DMA into a 3-stage ring; the
 // score MFMAs read K rows with ds_read_b128, the second product reads V^T (forward) or K^T (dQ) straight from the
@@ -251,8 +254,25 @@ __device__ __forceinline__ bf16x8 scale_frag(bf16x8 v, float p2) {
     return r;
 }
 
-// attention_fwd3.hip / attention_bwd3.hip
+// opt in to more than 48 KiB of dynamic LDS
+template <typename K> int set_lds(K kern, size_t bytes) {
+    if (bytes > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
+// attention_fwd3.hip / attention_bwd3.hip: bf16, head_dim 64, K / V rows within kvdma_ok
 int launch_fwd3_bf16(const AttnParams& p, hipStream_t st);
 int launch_dq3_bf16(const AttnParams& p, hipStream_t st);
+// attention_dkv.hip: bf16, head_dim 64, behind either dQ kernel
+int launch_dkv_bf16(const AttnParams& p, hipStream_t st);
+// attention_generic.hip: dtype GF_F32 / GF_BF16 (else GF_ERR_DTYPE), D in {32, 64, 128}; GF_ERR_UNSUPPORTED past 160 KiB of LDS.
+// launch_dq_generic alone is the dQ half in front of launch_dkv_bf16; launch_bwd_generic is dQ (ATTN_PLAIN_STATS) + generic dK/dV
+int launch_fwd_generic(const AttnParams& p, hipStream_t st, int dtype, int D);
+int launch_dq_generic(const AttnParams& p, hipStream_t st, int dtype, int D);
+int launch_bwd_generic(const AttnParams& p, hipStream_t st, int dtype, int D);
 
 }  // namespace gfattn

@@ -10,7 +10,7 @@ integration.
 What runs where
   * linear layers: hipBLASLt through torch (plain library GEMMs);
   * rotary + self attention, bidirectional cross attention (forward and backward):
-    hand-written MFMA flash kernels (csrc/attention.hip), fed by the fused projections in
+    hand-written MFMA flash kernels (csrc/attention*.hip), fed by the fused projections in
     place — no [B,H,N,N] tensor exists;
   * LayerNorm+GELU of the FFN: one fused HIP kernel each way (csrc/elementwise.hip);
   * assignment heads (lightglue.py:256-309): row/column log-sum-exp, arg-max and the

@@ -9,7 +9,7 @@ What runs where
     stacked) on ``gf_gemm`` (forward and input gradient, fused bias / two-source concat) and
     ``gf_linear_dw`` (weight gradient); only the 3-channel input layer of the keypoint
     encoder (K = 3) falls outside the kernel's plans and uses the library;
-  * attention (superglue.py:112-135): the MFMA flash kernels of csrc/attention.hip.  The
+  * attention (superglue.py:112-135): the MFMA flash kernels of csrc/attention*.hip.  The
     reference puts the head index FASTEST in the channel dimension (``view(b, dim, h, n)``);
     the projection weight rows (and the merge weight columns) are gathered once so the kernels
     see ``[.., head, channel]`` with contiguous channels — no activation shuffles;

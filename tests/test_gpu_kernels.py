@@ -77,6 +77,40 @@ def test_attention_strided_views_and_spike():
     torch.testing.assert_close(o.cpu().double(), ref, rtol=1e-4, atol=1e-4)
 
 
+def test_attention_bf16_kv_rows_past_buffer_descriptor_range():
+    """bf16, head_dim 64, K and V as views of one 1 GiB buffer with a token stride of 2^22 elements: Nk * stride = 2^29 is
+    the first extent the buffer-descriptor (LDS-DMA) kernels reject, so the forward and dQ run on the register-staged
+    kernels (dK/dV stays on the bf16 kernel).  Same reference and bounds as test_attention_fwd_bwd."""
+    B, H, Nq, Nk, D, STRIDE = 1, 2, 100, 128, 64, 1 << 22
+    g = torch.Generator().manual_seed(11)
+    q, k, v, do = (torch.randn(B, n, H, D, generator=g, dtype=torch.float64) for n in (Nq, Nk, Nk, Nq))
+    k = k * (1 + torch.arange(D, dtype=torch.float64) / D)
+    v = v + torch.arange(Nk, dtype=torch.float64)[None, :, None, None] / Nk
+    buf = torch.empty(Nk * STRIDE, dtype=torch.bfloat16, device=DEV)        # only the rows the views touch are written
+    kv = buf.view(Nk, STRIDE)[:, :2 * H * D].view(Nk, 2, H, D)
+    kv[:, 0].copy_(k[0])
+    kv[:, 1].copy_(v[0])
+    kd, vd = (kv[None, :, i].detach().requires_grad_(True) for i in (0, 1))
+    assert kd.stride(1) == STRIDE and vd.stride(1) == STRIDE and Nk * STRIDE == 1 << 29
+    qd = q.to(DEV, torch.bfloat16).requires_grad_(True)
+    dod = do.to(DEV, torch.bfloat16)
+    qr, kr, vr = (t.detach().to(torch.float64).cpu().requires_grad_(True) for t in (qd, kd, vd))
+    oref, lse_ref = _attn_ref(qr, kr, vr, D ** -0.5)
+    (oref * dod.cpu().double()).sum().backward()
+
+    o = ops.attention(qd, kd, vd)
+    (o * dod).sum().backward()
+    torch.testing.assert_close(o.detach().cpu().double(), oref.detach(), **_tols(torch.bfloat16))
+    for name, a, b in (("dq", qd.grad, qr.grad), ("dk", kd.grad, kr.grad), ("dv", vd.grad, vr.grad)):
+        scale = max(b.abs().max().item(), 1e-2)
+        torch.testing.assert_close(a.cpu().double() / scale, b / scale, msg=lambda m: f"{name}: {m}",
+                                   **_tols(torch.bfloat16))
+    _, lse = ops.attn_fwd_raw(qd.detach(), kd.detach(), vd.detach(), D ** -0.5)
+    torch.testing.assert_close(lse.cpu().double(), lse_ref.detach(), rtol=1e-4, atol=3e-2)
+    del buf, kv, kd, vd
+    torch.cuda.empty_cache()
+
+
 @pytest.mark.parametrize("B,H,Nq,Nk", [(2, 4, 256, 256), (1, 2, 100, 333)])
 def test_attention_premultiplied_operands(B, H, Nq, Nk):
     """scale = ln 2 with head_dim^-1/2 * log2(e) already folded into q (ops.attn_premul: what LightGlue's projections do):

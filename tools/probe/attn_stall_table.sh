@@ -1,6 +1,6 @@
 #!/bin/bash
 # Stall budget of the self-attention backward (round-5 review item 4): probe builds of the attention translation units with
-# ONE ingredient of the dK/dV or the dQ loop removed (GF_DKV_ABL / GF_DQ3_ABL bits, csrc/attention.hip, attention_bwd3.hip),
+# ONE ingredient of the dK/dV or the dQ loop removed (GF_DKV_ABL / GF_DQ3_ABL bits, csrc/attention_dkv.hip, attention_bwd3.hip),
 # timed in one process against the shipped form (tools/probe/time_attn.py, B2 = 64 images x 4 heads x 2048^2, scale = ln 2).
 #   build container:  bash tools/probe/attn_stall_table.sh build
 #   GPU box:          bash tools/probe/attn_stall_table.sh run > gpurun_out/attn_stall.txt
@@ -10,7 +10,7 @@ V="base:  dkv1:-DGF_DKV_ABL=1 dkv2:-DGF_DKV_ABL=2 dkv4:-DGF_DKV_ABL=4 dkv8:-DGF_
 if [ "$1" = build ]; then
   args=()
   for v in $V; do args+=("st_${v%%:*}" "${v#*:}"); done
-  # four at a time (8 build-container CPUs, 3 translation units each)
+  # four at a time (8 build-container CPUs; one compile at a time per variant)
   for ((i = 0; i < ${#args[@]}; i += 8)); do bash build_attn_variants.sh "${args[@]:i:8}"; done
   ls -la libv_st_*.so | wc -l
 else
