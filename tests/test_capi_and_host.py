@@ -136,6 +136,72 @@ def test_precast_cache_follows_parameter_versions():
         assert id(w) not in ops._LP_CACHE
 
 
+def test_ops_package_surface_and_global_state(monkeypatch):
+    """glue_factory_amd.ops (`pkg` here, so that this test adds nothing to its own scan) is a package of one sub-module per
+    kernel family: (a) every attribute of it that the repository names resolves on the package, (b) each mutable global
+    container is the SAME object on the package and in its home module, (c) the rebindable switches are attributes of the
+    package alone and their consumers read them there at call time."""
+    import glob
+    import types
+    from glue_factory_amd import lib, ops as pkg
+    assert os.path.basename(pkg.__file__) == "__init__.py"
+
+    # (a) the names used by the modules that import `ops` from this package
+    files = [os.path.join(ROOT, "bench.py")] + glob.glob(os.path.join(ROOT, "tests", "*.py"))
+    files += glob.glob(os.path.join(ROOT, "tools", "**", "*.py"), recursive=True)
+    files += glob.glob(os.path.join(ROOT, "glue-factory_amd", "**", "*.py"), recursive=True)
+    imports_ops = re.compile(r"^\s*from\s+(glue_factory_amd|\.\.?)\s+import\s+.*\bops\b", re.M)
+    used = set()
+    for path in files:
+        text = open(path).read()
+        if imports_ops.search(text):
+            used |= set(re.findall(r"\b_?ops\.([A-Za-z_]\w*)", text))
+    missing = sorted(n for n in used if not hasattr(pkg, n))
+    assert not missing, missing
+    assert len(used) >= 59, len(used)          # distinct names this scan found while the package was still one module
+
+    # (b) one home per container, re-exported by identity
+    homes = {"_LP_CACHE": pkg._params, "_LP_PTR": pkg._params, "_LP_T": pkg._params, "_LP_FLAT": pkg._params,
+             "LIBRARY_GEMMS": pkg._linear, "_SPARSE_SUMS": pkg._nll, "COLLECTIVES": pkg._batchnorm}
+    subs = [m for n, m in vars(pkg).items() if isinstance(m, types.ModuleType) and m.__name__ == pkg.__name__ + "." + n]
+    assert len(subs) == 9
+    for name, home in homes.items():
+        assert getattr(pkg, name) is getattr(home, name), name
+        assert [m for m in subs if hasattr(m, name)] == [home], name
+    cache = pkg._LP_CACHE
+    pkg.invalidate_precast()                   # ... and mutated in place, never rebound
+    assert pkg._LP_CACHE is cache is pkg._params._LP_CACHE
+
+    # (c) the switches: no copy in any sub-module
+    for name in ("XBWD_ENABLED", "FOLD_ENABLED", "REPLAY_GATE", "FORCE_SYNC_BN"):
+        assert hasattr(pkg, name) and not [m.__name__ for m in subs if hasattr(m, name)], name
+
+    class Consulted(Exception):
+        pass
+
+    class Sentinel:
+        def __bool__(self):
+            raise Consulted
+
+    def launched(*a, **k):
+        raise AssertionError("a consumer ignored the package switch and went on to the library")
+    monkeypatch.setattr(lib, "load", launched)
+    # _CrossAttentionStacked.backward takes the truth value of the package's XBWD_ENABLED before it picks a kernel
+    p = torch.zeros(2, 64, 2, 4, 64, dtype=torch.bfloat16)
+    ctx = types.SimpleNamespace(saved_tensors=(p, torch.zeros(2, 64, 4, 64, dtype=torch.bfloat16), torch.zeros(2, 4, 64)),
+                                scale=pkg.LN2)
+    monkeypatch.setattr(pkg, "XBWD_ENABLED", Sentinel())
+    with pytest.raises(Consulted):
+        pkg._attention._CrossAttentionStacked.backward(ctx, torch.zeros(2, 64, 4, 64, dtype=torch.bfloat16))
+    # folded_linear: a prepared fold is ignored while the package's FOLD_ENABLED is off, and consulted while it is on
+    monkeypatch.setitem(pkg._LP_FLAT, ("t_fold", torch.bfloat16), {"derived": {"f": {"fold": (1, 1, 1, 1, 0)}}})
+    monkeypatch.setattr(pkg, "FOLD_ENABLED", False)
+    assert pkg.folded_linear("t_fold", torch.bfloat16, "f", None, None, None, None) is None
+    monkeypatch.setattr(pkg, "FOLD_ENABLED", Sentinel())
+    with pytest.raises(Consulted):
+        pkg.folded_linear("t_fold", torch.bfloat16, "f", None, None, None, None)
+
+
 def test_sinkhorn_resident_plan_is_consistent():
     """gf_sinkhorn_plan (host-only): the distribution of the chip-resident Sinkhorn sweeps (csrc/sinkhorn_resident.h) over a
     256-CU device -- every pair gets whole workgroups, every row a wave, the rows of a wave fit its registers + LDS share, the

@@ -1,5 +1,6 @@
 """Same-process A/B of a python-level switch of the matcher step (box-to-box spread of the pool is +-5 %, so only
 same-process numbers decide).  Usage: python tools/probe/ab_matcher.py [--model lightglue|superglue|gluestick] [--switch FOLD_ENABLED]
+(the switch is an attribute of the glue_factory_amd.ops package: FOLD_ENABLED, XBWD_ENABLED).
 Builds one captured TrainStep per setting and alternates timed rounds A B A B ..."""
 import argparse
 import os
