@@ -1,4 +1,4 @@
-// Chip-resident Sinkhorn sweeps (included into sinkhorn.hip's anonymous namespace).
+// Chip-resident Sinkhorn sweeps: the third tier of gf_sinkhorn_fwd / _bwd (selected by sinkhorn.hip).
 //
 // The streaming fast path (skf_*) reads the whole coupling matrix from HBM once per iteration: 100 iterations
 // of superglue.py:186-191 = 100 sweeps of 537 MB at B = 32, N = 2048, and every sweep is two dependent launches.
@@ -37,39 +37,20 @@
 // the end of the kernel every wave of the pair overwrites its rows of the last iterate (forward: u^T, backward: ubar^1)
 // with NaN -- the pair's output / gradient is NaN in every row, the loss is NaN, and TrainStep's device-side skip flag
 // (train.py:477-480) drops the update.  Never a silently wrong number, never a hung device.
+#include <atomic>
+
+#include "sinkhorn_common.h"
+
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "sinkhorn_resident.h: the same-XCD hand-off is written against gfx950's cache hierarchy (see skr_same_xcd_allowed)"
+#error "sinkhorn_resident.hip: the same-XCD hand-off is written against gfx950's cache hierarchy (see skr_same_xcd_allowed)"
 #endif
+
+using namespace gfsk;
+
+namespace {
+
 constexpr int SKR_RR = 12;                 // rows of a wave that live in registers
-constexpr int SKR_MAX_BC = 16;             // pairs per launch (counter slots; the failure flags follow them)
 constexpr unsigned SKR_DEFAULT_WAIT_MS = 10000;
-
-struct SkrPlan {
-    int bc, wpp, nw, base, extra, cs, nsm;
-    size_t lds;
-};
-
-struct SkrArgs {
-    const float* Zraw;          // forward, round 6: the couplings themselves [bc, R, C] -- scaled by log2(e) while they are loaded,
-                                // rows only 4-byte aligned (C = N + 1): no pre-scaled padded copy is made for the resident forward
-    float* out;                 // forward, round 6: out = Z + u + v - norm written by the kernel's last iteration (null: not fused)
-    const float* Zp;            // backward: [bc, R, Cp] prescaled padded copy
-    float* part;                // [bc, nw, Cp] per-wave column partials
-    unsigned* ctr;              // [4 SKR_MAX_BC]: barrier counters, failure flags, XCD masks, same-XCD counters; zeroed before the launch
-    int safe_only;              // 1: placement-independent (write-through) hand-offs even when a pair sits on one XCD
-    long long wait_ticks;       // bound of every wait in wall_clock64() ticks
-    float* colA;                // [bc, Cp]  forward: running v (log2 units); backward: a2p
-    float* colB;                // [bc, Cp]  backward: vbp
-    float* u_hist;              // forward: written; backward: read           (chunk-offset, iteration stride ustride)
-    float* v_hist;
-    const float* base_row;      // backward: rowsum(G) of the chunk (k == T)
-    float* ubar_hist;           // backward: written (index k - 1)
-    float* vbar_hist;           // backward: written (index k - 1)
-    size_t ustride, vstride;
-    int iters;
-    SkrPlan d;
-    Geo g;
-};
 
 __global__ void skr_reset(unsigned* ctr) {
     if (threadIdx.x < 4 * SKR_MAX_BC) ctr[threadIdx.x] = 0u;
@@ -498,6 +479,10 @@ __global__ __launch_bounds__(256, 1) void skr_kernel(const SkrArgs a) {
     }
 }
 
+}  // namespace
+
+namespace gfsk {
+
 // `schedule` argument of gf_sinkhorn_fwd / _bwd / _plan, bits 0-1: 0 = streaming kernels only, 1 = resident from SKR_MIN_BC
 // pairs per launch, 2 = resident whenever the problem fits (tests: small batches too); bit 2: placement-independent
 // (write-through) hand-offs only, i.e. no same-XCD fast path (A/B tests); bits 8-31: bound of every inter-
@@ -547,7 +532,7 @@ int skr_cus() {                            // CU count of the CURRENT device (as
 // that L2, HW_REG_XCC_ID naming the XCD.  It is therefore enabled per architecture, at run time, and nowhere else: gfx950
 // (MI350X / MI355X; measured bit-identical to the write-through protocol, tests/test_gpu_sinkhorn_safety.py).  Any other
 // device -- and any failure to ask -- takes the placement-independent protocol.
-bool skr_same_xcd_allowed() {
+static bool skr_same_xcd_allowed() {
     // (an immutable fact about a device, remembered per device ordinal: 0 unknown, 1 yes, 2 no -- not a setting)
     static std::atomic<int> known[64];
     int dev = 0;
@@ -565,7 +550,7 @@ bool skr_same_xcd_allowed() {
     return k == 1;
 }
 
-long long skr_wait_ticks(int schedule) {   // the call's wait bound in wall_clock64() ticks of the CURRENT device
+static long long skr_wait_ticks(int schedule) {   // the call's wait bound in wall_clock64() ticks of the CURRENT device
     const unsigned ms = ((unsigned)schedule >> 8) ? ((unsigned)schedule >> 8) : SKR_DEFAULT_WAIT_MS;
     int dev = 0, khz = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -573,7 +558,7 @@ long long skr_wait_ticks(int schedule) {   // the call's wait bound in wall_cloc
     return (long long)ms * khz;
 }
 
-template <bool BWD> int skr_launch(const SkrArgs& a, hipStream_t st) {
+template <bool BWD> static int skr_launch(const SkrArgs& a, hipStream_t st) {
     skr_reset<<<1, 64, 0, st>>>(a.ctr);
     const dim3 grid((unsigned)(a.d.wpp * a.d.bc));
 #define SKR_CASE(NSM_)                                                                                                 \
@@ -591,3 +576,20 @@ template <bool BWD> int skr_launch(const SkrArgs& a, hipStream_t st) {
 #undef SKR_CASE
     return (int)hipGetLastError();
 }
+
+int skr_fwd_launch(const SkrArgs& a, hipStream_t st) { return skr_launch<false>(a, st); }
+int skr_bwd_launch(const SkrArgs& a, hipStream_t st) { return skr_launch<true>(a, st); }
+
+// The caller adds the chunk's pointers, d.bc and, per direction: forward Zraw / out, backward base_row / ubar_hist / vbar_hist.
+SkrArgs skr_shared_args(const Geo& g, const Ws& w, const SkrPlan& d, int iters, int schedule) {
+    SkrArgs a{};
+    a.Zp = w.zp; a.part = w.part; a.ctr = w.ctr;
+    a.colA = w.a2p; a.colB = w.vbp;                   // 16-byte aligned [B, Cp] scratch (free in the forward)
+    a.ustride = (size_t)g.B * g.R; a.vstride = (size_t)g.B * g.C;
+    a.iters = iters; a.d = d; a.g = g;
+    a.wait_ticks = skr_wait_ticks(schedule);
+    a.safe_only = ((schedule >> 2) & 1) || !skr_same_xcd_allowed();
+    return a;
+}
+
+}  // namespace gfsk

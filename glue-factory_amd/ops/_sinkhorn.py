@@ -1,4 +1,4 @@
-"""Log-domain Sinkhorn optimal transport (csrc/sinkhorn.hip)."""
+"""Log-domain Sinkhorn optimal transport (csrc/sinkhorn*.hip: entry points and tier selection in sinkhorn.hip)."""
 import os
 
 import torch
@@ -52,7 +52,7 @@ class _Sinkhorn(torch.autograd.Function):
 
 def sinkhorn_schedule(mode=None, wait_ms=None, safe_handoff=None):
     """The `schedule` argument of gf_sinkhorn_fwd / _bwd (include/gf_amd.h): mode 0 = streaming kernels only, 1 = chip-resident
-    sweeps from 5 pairs per launch (default), 2 = resident whenever the problem fits (csrc/sinkhorn_resident.h); wait_ms = bound
+    sweeps from 5 pairs per launch (default), 2 = resident whenever the problem fits (csrc/sinkhorn_resident.hip); wait_ms = bound
     of every inter-workgroup wait of the resident kernel (default 10 s; a pair whose wait expires comes out as NaN).
     Host-side knobs GF_SINKHORN_RESIDENT / GF_SINKHORN_WAIT_MS fill what the caller leaves open (the library itself reads no
     environment and keeps no setting)."""

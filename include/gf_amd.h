@@ -186,7 +186,7 @@ int gf_filter_matches(const float* max0, const int64_t* arg0, const int64_t* arg
  * ws: device workspace of gf_sinkhorn_ws_bytes(B, M, N, iters) bytes (same buffer size for both calls).
  * Two schedules of the same recurrence: streaming kernels (one sweep of Z per iteration, two launches each) and, for
  * N % 256 == 0, N <= 2048, chip-resident sweeps (a chunk of <= 8-16 pairs is loaded once and stays in registers + LDS for
- * all iterations, one persistent launch per chunk with per-pair workgroup barriers; csrc/sinkhorn_resident.h).
+ * all iterations, one persistent launch per chunk with per-pair workgroup barriers; csrc/sinkhorn_resident.hip).
  * `schedule` (per call; the library keeps no setting): bits 0-1 = 0 streaming only, 1 resident from 5 pairs per launch (the host
  * code's default), 2 resident whenever the problem fits; bit 2 = placement-independent hand-offs only (the resident kernel
  * otherwise publishes through the shared L2 when it FINDS all workgroups of a pair on one XCD at run time -- a speed path,

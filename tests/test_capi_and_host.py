@@ -203,7 +203,7 @@ def test_ops_package_surface_and_global_state(monkeypatch):
 
 
 def test_sinkhorn_resident_plan_is_consistent():
-    """gf_sinkhorn_plan (host-only): the distribution of the chip-resident Sinkhorn sweeps (csrc/sinkhorn_resident.h) over a
+    """gf_sinkhorn_plan (host-only): the distribution of the chip-resident Sinkhorn sweeps (csrc/sinkhorn_resident.hip) over a
     256-CU device -- every pair gets whole workgroups, every row a wave, the rows of a wave fit its registers + LDS share, the
     column phase covers every float4 column, the LDS request stays inside the CU -- for the benchmarked geometry and around it."""
     import ctypes
@@ -238,3 +238,49 @@ def test_sinkhorn_resident_plan_is_consistent():
     assert L.gf_sinkhorn_plan(32, 2048, 2048, 256, 0, 1, out) == 1 and tuple(out)[:5] == (8, 32, 128, 16, 1)
     assert L.gf_sinkhorn_plan(32, 2048, 2050, 256, 0, 1, out) == 0                      # N % 256 != 0: streaming
     assert L.gf_sinkhorn_plan(32, 2048, 2304, 256, 0, 1, out) == 0                      # N / 256 > 8
+
+
+# (M, N) across the tier boundaries of gf_sinkhorn_fwd / _bwd: ragged N (streaming only), N = 256 .. 2304 in steps the resident
+# layout accepts (N / 256 <= 8), N + 1 = 2304 (the last streaming width), N + 1 > 2304 (generic LDS kernels), M != N both ways,
+# and a width whose rows no longer fit the LDS (unsupported)
+_SK_SHAPES = ((255, 250), (256, 256), (1000, 512), (300, 1024), (1500, 1280), (2047, 2048), (2048, 2048), (2048, 2050),
+              (2048, 2303), (2304, 2304), (2400, 2400), (100, 3000), (3000, 300), (64, 9000))
+_SK_BATCHES = (1, 4, 5, 8, 9, 17, 32)
+# 64 / 256 / 304 CUs: parts that exist.  512: no such part, but the only way to a plan with more partial rows (4 waves per
+# workgroup x workgroups) than the workspace reserves (4 x 320) -- the condition that sends such a call to the streaming kernels
+_SK_NCU = (64, 256, 304, 512)
+
+
+def _sinkhorn_host_record(L):
+    out = (ctypes.c_int64 * 8)()
+    ws, plan = {}, {}
+    for B in _SK_BATCHES:
+        for M, N in _SK_SHAPES:
+            for iters in (0, 1, 100):
+                ws[f"{B},{M},{N},{iters}"] = int(L.gf_sinkhorn_ws_bytes(B, M, N, iters))
+            for ncu in _SK_NCU:
+                for bwd in (0, 1):
+                    for mode in (0, 1, 2):
+                        ok = int(L.gf_sinkhorn_plan(B, M, N, ncu, bwd, mode, out))
+                        plan[f"{B},{M},{N},{ncu},{bwd},{mode}"] = [ok] + ([int(v) for v in out] if ok == 1 else [])
+    return {"ws_bytes": ws, "plan": plan}
+
+
+def test_sinkhorn_host_arithmetic_matches_recorded():
+    """gf_sinkhorn_ws_bytes and gf_sinkhorn_plan (both host-only) against tests/golden/sinkhorn_host.json, this library's own
+    output recorded before the Sinkhorn translation unit was split: workspace sizes, which calls take the chip-resident
+    sweeps and with which distribution, over B x (M, N) x iterations x direction x schedule mode x CU count.  Whoever
+    changes the workspace layout or the tier selection on purpose re-records the file (json.dump of _sinkhorn_host_record)."""
+    import json
+    from glue_factory_amd import lib
+    got = _sinkhorn_host_record(lib.load())
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "sinkhorn_host.json")))
+    assert got["ws_bytes"] == want["ws_bytes"]
+    assert got["plan"] == want["plan"]
+    assert sum(v[0] == 1 for v in want["plan"].values()) > 100
+    # the fixture holds calls that the partial-row reservation alone keeps off the resident path (more CUs only shrink
+    # every other requirement of the plan)
+    def at256(key):
+        f = key.split(",")
+        return ",".join(f[:3] + ["256"] + f[4:])
+    assert any(k.split(",")[3] == "512" and v[0] == 0 and want["plan"][at256(k)][0] == 1 for k, v in want["plan"].items())

@@ -2,7 +2,8 @@
 the code paths that only a large batch takes.
 
   * Sinkhorn: the multi-chunk path (`batch_chunk()` splits B=32, N=2048 into 2 chunks of 16 with per-chunk pointer /
-    history-stride arithmetic, csrc/sinkhorn.hip) and the generic `sk_*` kernels (N+1 > 2304) against the fp64 oracle
+    history-stride arithmetic, csrc/sinkhorn.hip) and the generic `sk_*` kernels (N+1 > 2304, csrc/sinkhorn_generic.hip)
+    against the fp64 oracle
     of superglue.py:186-214 (oracle/sinkhorn_oracle.py), forward and backward; every pair of the big batch additionally
     against a single-chunk launch of the same pair;
   * batch consistency of the whole train step at B=32 (the 64-image x 4-head x 2048^2 launch geometry of the attention /

@@ -26,7 +26,7 @@ def test_sinkhorn_fwd_bwd_vs_reference_golden():
 
 
 @pytest.mark.parametrize("B,M,N,T", [(3, 130, 97, 7), (1, 1, 5, 3), (2, 300, 300, 0), (2, 2100, 2050, 2),
-                                     # N % 256 == 0: the chip-resident sweeps (csrc/sinkhorn_resident.h), ragged M, one and
+                                     # N % 256 == 0: the chip-resident sweeps (csrc/sinkhorn_resident.hip), ragged M, one and
                                      # several pairs per launch, rows in registers only / registers + LDS
                                      (3, 300, 256, 6), (2, 1000, 1024, 4), (5, 700, 512, 25), (11, 1500, 1280, 3),
                                      (1, 2048, 2048, 1)])

@@ -1,10 +1,11 @@
-"""time gf_sinkhorn_fwd / gf_sinkhorn_bwd of probe builds (B=32, N=2048, 100 iterations) in ONE process and check each
+"""time gf_sinkhorn_fwd / gf_sinkhorn_bwd of probe builds (B=32, M=N=2048, 100 iterations) in ONE process and check each
 against the first: python tools/probe/time_sinkhorn.py libv_a.so libv_b.so ...
 An argument of the form  path@0 / path@1  passes schedule 0 / 1 to the calls of that run (streaming vs chip-resident sweeps;
 ABI >= 14: the schedule is an argument of gf_sinkhorn_fwd / _bwd);
-GF_PROBE_B / GF_PROBE_T override the batch and the iteration count."""
+GF_PROBE_B / GF_PROBE_N / GF_PROBE_T override the batch, the keypoint count (N + 1 > 2304, e.g. 2400: the generic LDS
+kernels) and the iteration count."""
 import ctypes, os, sys, torch
-B, N, T = int(os.environ.get("GF_PROBE_B", 32)), 2048, int(os.environ.get("GF_PROBE_T", 100))
+B, N, T = (int(os.environ.get("GF_PROBE_" + k, d)) for k, d in (("B", 32), ("N", 2048), ("T", 100)))
 P, I = ctypes.c_void_p, ctypes.c_int
 g = torch.Generator(device="cuda").manual_seed(0)
 Z = torch.randn(B, N + 1, N + 1, device="cuda", generator=g) * 2
