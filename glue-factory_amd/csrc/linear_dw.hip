@@ -2,11 +2,25 @@
 //     dW[n][k] = sum_m dY[m][n] X[m][k],   db[n] = sum_m dY[m][n]        (M = B*N tokens ~ 1.3e5)
 // i.e. autograd's grad of F.linear (reference: every nn.Linear of lightglue.py:131-221, 271-290).
 // The library GEMM handles this "tiny output, huge reduction" shape poorly (0.16-0.26 ms per
-// call, 2/3 of all GEMM time of the step), so it is a hand-written split-M MFMA kernel:
-// each workgroup owns a 128x128 output tile and one slice of M, streams dY / X row tiles
-// through LDS TRANSPOSED (token axis contiguous, so MFMA fragments are 16-byte reads),
-// double-buffered with register prefetch, accumulates in fp32, and writes its partial tile to
-// a workspace; a second kernel sums the slices (deterministic, no atomics) into fp32 dW / db.
+// call, 2/3 of all GEMM time of the step), so it is hand-written.
+//
+// One scheme, three kernels.  The scheme (split-M): a workgroup owns one 128x128 tile of dW and one
+// slice of M (plan(): as many slices as fill one round of the chip; dw_tile(): which block gets
+// which), streams that slice's dY / X rows through LDS into MFMAs with fp32 accumulation, and writes
+// its partial tile to the workspace part[slice][Nout][K] (bias: bpart[slice][Nout]);
+// linear_dw_reduce then sums the slices into fp32 dW / db -- deterministic, no atomics.
+//
+// The kernels differ in how the rows get from global memory into MFMA fragments; select_kernel() is
+// the only place that chooses:
+//   linear_dw_dma_kernel  bf16, Nout % 128 == 0 and K % 128 == 0: LDS-DMA ring.  Every linear of the
+//                         benchmarked step, and the only tier that reads a two-source X (gf_linear_dw2).
+//   linear_dw_tr_kernel   bf16, any other Nout, K (multiples of 8): register-staged row-major tiles,
+//                         transposing LDS reads.
+//   linear_dw_f32_kernel  fp32 (parity mode), Nout, K multiples of 4: register-staged, tiles
+//                         transposed by the LDS stores.
+// Each was the fast path until the next replaced it on the shapes that one can take (the section
+// comments keep the measurements).  The two older ones stay as capability paths: the DMA tier's
+// staging is unguarded, 128 columns wide and bf16-only, so ragged shapes and fp32 need them.
 #include <cstdlib>
 #include <type_traits>
 #include "gf_common.h"
@@ -19,19 +33,88 @@
 namespace {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-template <typename T> struct DwLay {
-    static constexpr int VEC = 16 / sizeof(T);
-    static constexpr int LDT = 64 + VEC;            // transposed tile stride (16-byte aligned rows)
-    static constexpr int TILE = 128 * LDT;          // elements: [128 cols][64 tokens]
-    static constexpr int CPR = 128 / VEC;           // 16-byte chunks per 128-wide row slice
-    static constexpr int ITEMS = 32 * CPR / 256;    // (row pair, chunk) items per thread
-};
-template <typename T> struct PairT;
-template <> struct PairT<bf16_t> { typedef bf16x2 type; };
-template <> struct PairT<float> { typedef f32x2 type; };
+// ---------------------------------------------------------------------------------------------
+// Shared by the tiers: which tile and slice a block owns, the store of its partial tile, and the
+// bias partial of the two register-staged tiers.
+// ---------------------------------------------------------------------------------------------
+struct DwTile { int tn, tk, slice, m_begin, m_end; };
 
-template <typename T> struct DwRegs { u32x4 a[DwLay<T>::ITEMS], b[DwLay<T>::ITEMS]; };
+// Grid: ntile * (nslice rounded up to 8) blocks; a block whose slice begins at or past M has no work.
+// XCD-aware order: block b runs on XCD b % 8; all output tiles of one M-slice are given to the
+// same XCD back to back, so the dY / X row slabs they share are served by that XCD's L2 instead of
+// being re-read from HBM once per tile (4x the traffic at 512x512).  plan() counts on this order.
+// RAGGED (here and below): Nout or K need not be a multiple of 128, so the last tile may hang over.
+template <bool RAGGED>
+__device__ __forceinline__ DwTile dw_tile(int Nout, int K, int rows_per_slice, int M) {
+    const int ntk = RAGGED ? (K + 127) / 128 : K / 128;
+    const int ntile = (RAGGED ? (Nout + 127) / 128 : Nout / 128) * ntk;
+    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+    const int tile = j % ntile;
+    DwTile t;
+    t.slice = (j / ntile) * 8 + xcd;
+    t.tn = tile / ntk;
+    t.tk = tile % ntk;
+    t.m_begin = t.slice * rows_per_slice;
+    t.m_end = min(M, t.m_begin + rows_per_slice);
+    return t;
+}
+
+// acc[i][j] of the 2 x 2 waves (each 64 (n) x 64 (k)) -> pp[n][k], this slice's [Nout][K] partial.
+// C[n][k]: lane column = k (l31), rows n = crow(r, hi); wn, wk, l31, hi as the kernels compute them.
+template <bool RAGGED>
+__device__ __forceinline__ void store_partial(float* pp, const f32x16 (&acc)[2][2], int tn, int tk, int wn, int wk,
+                                              int l31, int hi, int Nout, int K) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int kk = tk * 128 + wk * 64 + j * 32 + l31;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int nn = tn * 128 + wn * 64 + i * 32 + crow(r, hi);
+                if (!RAGGED || (nn < Nout && kk < K)) pp[(int64_t)nn * K + kk] = acc[i][j][r];
+            }
+        }
+}
+
+// bpart[slice][tn's 128 columns] from per-thread column sums (tk == 0 blocks).  A thread's 16-byte chunk of the
+// 128-wide row (CPR = 128 / VEC chunks) is the same for every M-chunk, but the rows of a chunk are spread over the whole
+// workgroup: item it = tid + 256 i holds bsum[i][0 .. VEC) of chunk it % CPR, and the 256 ITEMS / CPR items of a chunk are
+// combined through LDS (`red`: the tile buffers, reused after the main loop's last barrier).
+template <int VEC, int ITEMS>
+__device__ __forceinline__ void bias_through_lds(float* red, const float (&bsum)[ITEMS][VEC], float* bpart, int slice, int tn, int Nout) {
+    constexpr int CPR = 128 / VEC;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        int it = threadIdx.x + 256 * i;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) red[it * VEC + e] = bsum[i][e];
+    }
+    __syncthreads();
+    for (int col = threadIdx.x; col < 128; col += 256) {
+        const int cc = col / VEC, e = col % VEC;
+        float v = 0.f;
+        for (int p = 0; p < 256 * ITEMS / CPR; ++p) v += red[(p * CPR + cc) * VEC + e];
+        if (tn * 128 + col < Nout) bpart[(int64_t)slice * Nout + tn * 128 + col] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// fp32: dY / X row tiles (64 tokens x 128 columns) go through LDS TRANSPOSED (token axis contiguous,
+// so MFMA fragments are 16-byte reads), double-buffered with register prefetch.  The transposition
+// is done by the staging stores: 4-byte pairs of two rows.
+// ---------------------------------------------------------------------------------------------
+constexpr int F32_VEC = 4;                      // floats per 16-byte chunk
+constexpr int F32_LDT = 64 + F32_VEC;           // transposed tile stride (16-byte aligned rows)
+constexpr int F32_TILE = 128 * F32_LDT;         // elements: [128 cols][64 tokens]
+constexpr int F32_CPR = 128 / F32_VEC;          // 16-byte chunks per 128-wide row slice
+constexpr int F32_ITEMS = 32 * F32_CPR / 256;   // (row pair, chunk) items per thread
+constexpr int F32_LDS = 4 * F32_TILE * 4;       // bytes: 2 buffers x (A^T tile | B^T tile)
+
+struct F32Regs { u32x4 a[F32_ITEMS], b[F32_ITEMS]; };
 
 // 8-element (16-byte) blocks of a transposed row are XOR-swizzled by the row's chunk index so that
 // the coalesced staging order (consecutive lanes = consecutive 16-byte chunks of one source row)
@@ -39,59 +122,42 @@ template <typename T> struct DwRegs { u32x4 a[DwLay<T>::ITEMS], b[DwLay<T>::ITEM
 __device__ __forceinline__ int dswz(int d, int pos) { return pos ^ (((d >> 3) & 7) << 3); }
 
 // rows [m0, m0+64) x cols [c0, c0+128) of a row-major [M, ld] matrix (zero beyond M / ncols)
-template <typename T>
-__device__ __forceinline__ void dw_load(DwRegs<T>& rg, const T* g, int64_t ld, int m0, int mend, int c0, int ncols) {
-    using L = DwLay<T>;
+__device__ __forceinline__ void f32_load(F32Regs& rg, const float* g, int64_t ld, int m0, int mend, int c0, int ncols) {
 #pragma unroll
-    for (int i = 0; i < L::ITEMS; ++i) {
+    for (int i = 0; i < F32_ITEMS; ++i) {
         int it = threadIdx.x + 256 * i;
-        int cc = it % L::CPR, p = it / L::CPR;
-        int r0 = m0 + 2 * p, r1 = r0 + 1, col = c0 + cc * L::VEC;
+        int cc = it % F32_CPR, p = it / F32_CPR;
+        int r0 = m0 + 2 * p, r1 = r0 + 1, col = c0 + cc * F32_VEC;
         u32x4 z = {0, 0, 0, 0};
         bool okc = col < ncols;
         rg.a[i] = (okc && r0 < mend) ? *reinterpret_cast<const u32x4*>(g + (int64_t)r0 * ld + col) : z;
         rg.b[i] = (okc && r1 < mend) ? *reinterpret_cast<const u32x4*>(g + (int64_t)r1 * ld + col) : z;
     }
 }
-template <typename T>
-__device__ __forceinline__ void dw_store(const DwRegs<T>& rg, T* ldsT) {
-    using L = DwLay<T>;
-    typedef typename PairT<T>::type pair_t;
+__device__ __forceinline__ void f32_store(const F32Regs& rg, float* ldsT) {
 #pragma unroll
-    for (int i = 0; i < L::ITEMS; ++i) {
+    for (int i = 0; i < F32_ITEMS; ++i) {
         int it = threadIdx.x + 256 * i;
-        int cc = it % L::CPR, p = it / L::CPR;
-        union { u32x4 u; T e[L::VEC]; } x, y;
+        int cc = it % F32_CPR, p = it / F32_CPR;
+        union { u32x4 u; float e[F32_VEC]; } x, y;
         x.u = rg.a[i];
         y.u = rg.b[i];
 #pragma unroll
-        for (int e = 0; e < L::VEC; ++e) {
-            pair_t pr = {x.e[e], y.e[e]};
-            const int d = cc * L::VEC + e;
-            *reinterpret_cast<pair_t*>(ldsT + d * L::LDT + dswz(d, 2 * p)) = pr;
+        for (int e = 0; e < F32_VEC; ++e) {
+            f32x2 pr = {x.e[e], y.e[e]};
+            const int d = cc * F32_VEC + e;
+            *reinterpret_cast<f32x2*>(ldsT + d * F32_LDT + dswz(d, 2 * p)) = pr;
         }
     }
 }
 
-// grid: (ntile_n * ntile_k, nslice); partial [nslice][Nout][K] fp32, bias partial [nslice][Nout]
-template <typename T>
-__global__ __launch_bounds__(256, 2) void linear_dw_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                                                           float* __restrict__ part, float* __restrict__ bpart,
-                                                           int M, int Nout, int K, int rows_per_slice) {
-    using L = DwLay<T>;
+__global__ __launch_bounds__(256, 2) void linear_dw_f32_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                               float* __restrict__ part, float* __restrict__ bpart,
+                                                               int M, int Nout, int K, int rows_per_slice) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    T* lds = reinterpret_cast<T*>(smem);           // 2 buffers x (A^T tile | B^T tile)
-    // XCD-aware order: block b runs on XCD b % 8; all output tiles of one M-slice are given to the
-    // same XCD back to back, so the dY / X row slabs they share are served by that XCD's L2 instead of
-    // being re-read from HBM once per tile (4x the traffic at 512x512).
-    const int ntk = (K + 127) / 128;
-    const int ntile = ((Nout + 127) / 128) * ntk;
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int tile = j % ntile;
-    const int slice = (j / ntile) * 8 + xcd;
-    const int tn = tile / ntk, tk = tile % ntk;
-    const int m_begin = slice * rows_per_slice, m_end = min(M, m_begin + rows_per_slice);
-    if (m_begin >= M) return;
+    float* lds = reinterpret_cast<float*>(smem);
+    const DwTile t = dw_tile<true>(Nout, K, rows_per_slice, M);
+    if (t.m_begin >= M) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     const int wn = wave >> 1, wk = wave & 1;       // 2 x 2 waves, each 64 (n) x 64 (k)
@@ -103,49 +169,49 @@ __global__ __launch_bounds__(256, 2) void linear_dw_kernel(const T* __restrict__
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    float bsum[L::ITEMS][L::VEC];
+    float bsum[F32_ITEMS][F32_VEC];
 #pragma unroll
-    for (int i = 0; i < L::ITEMS; ++i)
+    for (int i = 0; i < F32_ITEMS; ++i)
 #pragma unroll
-        for (int e = 0; e < L::VEC; ++e) bsum[i][e] = 0.f;
+        for (int e = 0; e < F32_VEC; ++e) bsum[i][e] = 0.f;
 
-    DwRegs<T> ra, rb;
+    F32Regs ra, rb;
     auto add_bias = [&]() {
-        if (tk == 0) {
+        if (t.tk == 0) {
 #pragma unroll
-            for (int i = 0; i < L::ITEMS; ++i) {
-                union { u32x4 u; T e[L::VEC]; } x0, x1;
+            for (int i = 0; i < F32_ITEMS; ++i) {
+                union { u32x4 u; float e[F32_VEC]; } x0, x1;
                 x0.u = ra.a[i];
                 x1.u = ra.b[i];
 #pragma unroll
-                for (int e = 0; e < L::VEC; ++e) bsum[i][e] += to_f32(x0.e[e]) + to_f32(x1.e[e]);
+                for (int e = 0; e < F32_VEC; ++e) bsum[i][e] += x0.e[e] + x1.e[e];
             }
         }
     };
-    const int nchunk = (m_end - m_begin + 63) / 64;
+    const int nchunk = (t.m_end - t.m_begin + 63) / 64;
     if (nchunk > 0) {
-        dw_load<T>(ra, dy, Nout, m_begin, m_end, tn * 128, Nout);
-        dw_load<T>(rb, x, K, m_begin, m_end, tk * 128, K);
+        f32_load(ra, dy, Nout, t.m_begin, t.m_end, t.tn * 128, Nout);
+        f32_load(rb, x, K, t.m_begin, t.m_end, t.tk * 128, K);
         add_bias();
-        dw_store<T>(ra, lds);
-        dw_store<T>(rb, lds + L::TILE);
+        f32_store(ra, lds);
+        f32_store(rb, lds + F32_TILE);
     }
     __syncthreads();
     for (int c = 0; c < nchunk; ++c) {
-        const T* At = lds + (c & 1) * 2 * L::TILE;
-        const T* Bt = At + L::TILE;
+        const float* At = lds + (c & 1) * 2 * F32_TILE;
+        const float* Bt = At + F32_TILE;
         if (c + 1 < nchunk) {
-            dw_load<T>(ra, dy, Nout, m_begin + (c + 1) * 64, m_end, tn * 128, Nout);
-            dw_load<T>(rb, x, K, m_begin + (c + 1) * 64, m_end, tk * 128, K);
+            f32_load(ra, dy, Nout, t.m_begin + (c + 1) * 64, t.m_end, t.tn * 128, Nout);
+            f32_load(rb, x, K, t.m_begin + (c + 1) * 64, t.m_end, t.tk * 128, K);
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {      // 64 tokens = 4 k-steps of 16
-            Frag<T> af[2], bf[2];
+            Frag<float> af[2], bf[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int dn = wn * 64 + i * 32 + l31, dk = wk * 64 + i * 32 + l31;
-                af[i] = ld_frag8(At + dn * L::LDT + dswz(dn, 16 * s + 8 * hi));
-                bf[i] = ld_frag8(Bt + dk * L::LDT + dswz(dk, 16 * s + 8 * hi));
+                af[i] = ld_frag8(At + dn * F32_LDT + dswz(dn, 16 * s + 8 * hi));
+                bf[i] = ld_frag8(Bt + dk * F32_LDT + dswz(dk, 16 * s + 8 * hi));
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -154,48 +220,18 @@ __global__ __launch_bounds__(256, 2) void linear_dw_kernel(const T* __restrict__
         }
         if (c + 1 < nchunk) {
             add_bias();
-            T* nb = lds + ((c + 1) & 1) * 2 * L::TILE;
-            dw_store<T>(ra, nb);
-            dw_store<T>(rb, nb + L::TILE);
+            float* nb = lds + ((c + 1) & 1) * 2 * F32_TILE;
+            f32_store(ra, nb);
+            f32_store(rb, nb + F32_TILE);
         }
         __syncthreads();
     }
-    // C[n][k]: lane column = k (l31), rows n = crow(r, hi)
-    float* pp = part + (int64_t)slice * Nout * K;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int kk = tk * 128 + wk * 64 + j * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nn = tn * 128 + wn * 64 + i * 32 + crow(r, hi);
-                if (nn < Nout && kk < K) pp[(int64_t)nn * K + kk] = acc[i][j][r];
-            }
-        }
-    if (tk == 0) {
-        // chunk cc = it % CPR is fixed per thread across chunks; its 32 row pairs p = it / CPR are spread
-        // over the whole workgroup -> combine through LDS (reused after the last barrier)
-        float* red = reinterpret_cast<float*>(smem);
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < L::ITEMS; ++i) {
-            int it = threadIdx.x + 256 * i;
-#pragma unroll
-            for (int e = 0; e < L::VEC; ++e) red[it * L::VEC + e] = bsum[i][e];
-        }
-        __syncthreads();
-        for (int col = threadIdx.x; col < 128; col += 256) {
-            const int cc = col / L::VEC, e = col % L::VEC;
-            float v = 0.f;
-            for (int p = 0; p < 32; ++p) v += red[(p * L::CPR + cc) * L::VEC + e];
-            if (tn * 128 + col < Nout) bpart[(int64_t)slice * Nout + tn * 128 + col] = v;
-        }
-    }
+    store_partial<true>(part + (int64_t)t.slice * Nout * K, acc, t.tn, t.tk, wn, wk, l31, hi, Nout, K);
+    if (t.tk == 0) bias_through_lds(lds, bsum, bpart, t.slice, t.tn, Nout);
 }
 
 // ---------------------------------------------------------------------------------------------
-// bf16 fast path: ROW-MAJOR LDS tiles (16-byte coalesced global loads -> conflict-free 16-byte LDS
+// bf16, any Nout / K: ROW-MAJOR LDS tiles (16-byte coalesced global loads -> conflict-free 16-byte LDS
 // stores, no transposing stores at all) read back through gfx950's transposing LDS load
 // ds_read_b64_tr_b16.  Semantics (probed on hardware, tools/probe/tr.hip): inside each group of 16
 // lanes, lane s supplies the address of 4 consecutive bf16; output lane i receives, for j = 0..3,
@@ -205,8 +241,7 @@ __global__ __launch_bounds__(256, 2) void linear_dw_kernel(const T* __restrict__
 // ---------------------------------------------------------------------------------------------
 constexpr int TR_LD = 128 + 32;                 // row stride (bf16): 320 B -> rows 16 banks apart (of 64)
 constexpr int TR_TILE = 64 * TR_LD;
-
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+constexpr int TR_LDS = 4 * TR_TILE * 2;         // bytes: 2 buffers x (dY tile | X tile), row-major
 
 __device__ __forceinline__ u32x2 ds_read_tr16(const bf16_t* p) {
     u32x2 v;
@@ -251,18 +286,9 @@ __global__ __launch_bounds__(256, 2) void linear_dw_tr_kernel(const bf16_t* __re
                                                               float* __restrict__ part, float* __restrict__ bpart,
                                                               int M, int Nout, int K, int rows_per_slice) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    bf16_t* lds = reinterpret_cast<bf16_t*>(smem);          // 2 buffers x (dY tile | X tile), row-major
-    // XCD-aware order: block b runs on XCD b % 8; all output tiles of one M-slice are given to the
-    // same XCD back to back, so the dY / X row slabs they share are served by that XCD's L2 instead of
-    // being re-read from HBM once per tile (4x the traffic at 512x512).
-    const int ntk = (K + 127) / 128;
-    const int ntile = ((Nout + 127) / 128) * ntk;
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int tile = j % ntile;
-    const int slice = (j / ntile) * 8 + xcd;
-    const int tn = tile / ntk, tk = tile % ntk;
-    const int m_begin = slice * rows_per_slice, m_end = min(M, m_begin + rows_per_slice);
-    if (m_begin >= M) return;
+    bf16_t* lds = reinterpret_cast<bf16_t*>(smem);
+    const DwTile t = dw_tile<true>(Nout, K, rows_per_slice, M);
+    if (t.m_begin >= M) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     const int wn = wave >> 1, wk = wave & 1;
@@ -287,19 +313,19 @@ __global__ __launch_bounds__(256, 2) void linear_dw_tr_kernel(const bf16_t* __re
     // unroll-by-2), the LDS image one chunk ahead.
     TrRegs ra0, rb0, ra1, rb1;
     auto load = [&](TrRegs& a_, TrRegs& b_, int c) {
-        tr_load(a_, dy, Nout, m_begin + c * 64, m_end, tn * 128, Nout);
-        tr_load(b_, x, K, m_begin + c * 64, m_end, tk * 128, K);
+        tr_load(a_, dy, Nout, t.m_begin + c * 64, t.m_end, t.tn * 128, Nout);
+        tr_load(b_, x, K, t.m_begin + c * 64, t.m_end, t.tk * 128, K);
     };
     auto stash = [&](TrRegs& a_, TrRegs& b_, int c) {
         tr_mask(a_);
         tr_mask(b_);
-        if (tk == 0) {
+        if (t.tk == 0) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                union { u32x4 u; bf16_t e[8]; } t;
-                t.u = a_.v[i];
+                union { u32x4 u; bf16_t e[8]; } v;
+                v.u = a_.v[i];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) bsum[i][e] += (float)t.e[e];
+                for (int e = 0; e < 8; ++e) bsum[i][e] += (float)v.e[e];
             }
         }
         bf16_t* nb = lds + (c & 1) * 2 * TR_TILE;
@@ -360,7 +386,7 @@ __global__ __launch_bounds__(256, 2) void linear_dw_tr_kernel(const bf16_t* __re
         wait_all(f1);
         mfmas(f1);
     };
-    const int nchunk = (m_end - m_begin + 63) / 64;
+    const int nchunk = (t.m_end - t.m_begin + 63) / 64;
     if (nchunk > 0) {
         load(ra0, rb0, 0);
         if (nchunk > 1) load(ra1, rb1, 1);
@@ -380,32 +406,12 @@ __global__ __launch_bounds__(256, 2) void linear_dw_tr_kernel(const bf16_t* __re
             __syncthreads();
         }
     }
-    float* pp = part + (int64_t)slice * Nout * K;
+    store_partial<true>(part + (int64_t)t.slice * Nout * K, acc, t.tn, t.tk, wn, wk, l31, hi, Nout, K);
+    if (t.tk == 0) {
+        float tot[1][8];                        // a thread's four items share one column chunk (tid & 15)
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int kk = tk * 128 + wk * 64 + j * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nn = tn * 128 + wn * 64 + i * 32 + crow(r, hi);
-                if (nn < Nout && kk < K) pp[(int64_t)nn * K + kk] = acc[i][j][r];
-            }
-        }
-    if (tk == 0) {
-        // column chunk cc = tid & 15 is fixed per thread; its rows are spread over the workgroup
-        float* red = reinterpret_cast<float*>(smem);
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-            red[threadIdx.x * 8 + e] = bsum[0][e] + bsum[1][e] + bsum[2][e] + bsum[3][e];
-        __syncthreads();
-        for (int col = threadIdx.x; col < 128; col += 256) {
-            const int cc = col >> 3, e = col & 7;
-            float v = 0.f;
-            for (int r = 0; r < 16; ++r) v += red[(r * 16 + cc) * 8 + e];
-            if (tn * 128 + col < Nout) bpart[(int64_t)slice * Nout + tn * 128 + col] = v;
-        }
+        for (int e = 0; e < 8; ++e) tot[0][e] = bsum[0][e] + bsum[1][e] + bsum[2][e] + bsum[3][e];
+        bias_through_lds(reinterpret_cast<float*>(smem), tot, bpart, t.slice, t.tn, Nout);
     }
 }
 
@@ -419,6 +425,7 @@ __global__ __launch_bounds__(256, 2) void linear_dw_tr_kernel(const bf16_t* __re
 // MFMA against a fragment of ones.
 // ---------------------------------------------------------------------------------------------
 constexpr int DM_ROWS = 32, DM_TILE = DM_ROWS * 256, DM_STAGE = 2 * DM_TILE, DM_NSTAGE = 4;
+constexpr int DM_LDS = DM_NSTAGE * DM_STAGE;    // bytes
 typedef __attribute__((address_space(3))) void dm_lds_void;
 typedef const __attribute__((address_space(1))) void dm_glb_void;
 
@@ -543,17 +550,7 @@ __device__ __forceinline__ void dm_body(const bf16_t* __restrict__ dy, const bf1
         if (c + 2 < nchunk) step(c + 2, std::integral_constant<int, 2>{});
         if (c + 3 < nchunk) step(c + 3, std::integral_constant<int, 3>{});
     }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int kk = tk * 128 + wk * 64 + j * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nn = tn * 128 + wn * 64 + i * 32 + crow(r, hi);
-                pp[(int64_t)nn * K + kk] = acc[i][j][r];
-            }
-        }
+    store_partial<false>(pp, acc, tn, tk, wn, wk, l31, hi, Nout, K);
     if (BIAS && wk == 0 && l31 == 0) {          // every column of the ones-product holds the row sums
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -566,30 +563,26 @@ __global__ __launch_bounds__(256, 2) void linear_dw_dma_kernel(const bf16_t* __r
                                                                const bf16_t* __restrict__ x2, int K1,
                                                                float* __restrict__ part, float* __restrict__ bpart,
                                                                int M, int Nout, int K, int rows_per_slice) {
-    const int ntk = K / 128;
-    const int ntile = (Nout / 128) * ntk;
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int tile = j % ntile;
-    const int slice = (j / ntile) * 8 + xcd;
-    const int tn = tile / ntk, tk = tile % ntk;
-    const int m_begin = slice * rows_per_slice, m_end = min(M, m_begin + rows_per_slice);
-    if (m_begin >= M) return;
-    float* pp = part + (int64_t)slice * Nout * K;
-    float* bp = bpart + (int64_t)slice * Nout;
-    const bf16_t* xs = x + (int64_t)tk * 128;
+    const DwTile t = dw_tile<false>(Nout, K, rows_per_slice, M);
+    if (t.m_begin >= M) return;
+    float* pp = part + (int64_t)t.slice * Nout * K;
+    float* bp = bpart + (int64_t)t.slice * Nout;
+    const bf16_t* xs = x + (int64_t)t.tk * 128;
     int ldx = K;
     if (x2 != nullptr) {                         // x = [x1 (K1 columns) | x2 (K - K1 columns)], K1 % 128 == 0
-        if (tk * 128 < K1) { ldx = K1; }
-        else { xs = x2 + (int64_t)(tk * 128 - K1); ldx = K - K1; }
+        if (t.tk * 128 < K1) { ldx = K1; }
+        else { xs = x2 + (int64_t)(t.tk * 128 - K1); ldx = K - K1; }
     }
-    if (tk == 0) dm_body<true>(dy, xs, ldx, pp, bp, M, Nout, K, m_begin, m_end, tn, tk);
-    else dm_body<false>(dy, xs, ldx, pp, bp, M, Nout, K, m_begin, m_end, tn, tk);
+    if (t.tk == 0) dm_body<true>(dy, xs, ldx, pp, bp, M, Nout, K, t.m_begin, t.m_end, t.tn, t.tk);
+    else dm_body<false>(dy, xs, ldx, pp, bp, M, Nout, K, t.m_begin, t.m_end, t.tn, t.tk);
 }
 
+// ---------------------------------------------------------------------------------------------
 // Sum of the per-slice partials.  A workgroup covers 64 float4 columns with FOUR slice groups (one per wave,
 // slices k = g mod 4) that meet in LDS: a 256x256 output with 64 slices is 256 workgroups of 16-deep
 // chains instead of 64 workgroups of 64-deep ones (the kernel is latency-, not bandwidth-bound).
 // Blocks past the weight columns reduce the bias partials the same way.  Deterministic (no atomics).
+// ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void linear_dw_reduce(const float* __restrict__ part, const float* __restrict__ bpart,
                                                         float* __restrict__ dw, float* __restrict__ db, int nslice,
                                                         int64_t nw, int Nout, int nwb) {
@@ -627,6 +620,9 @@ __global__ __launch_bounds__(256) void linear_dw_reduce(const float* __restrict_
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host: slice plan, tier selection, the one launch sequence.
+// ---------------------------------------------------------------------------------------------
 struct DwPlan { int ntile, nslice, rows; };
 DwPlan plan(int M, int Nout, int K) {
     DwPlan p;
@@ -647,22 +643,51 @@ DwPlan plan(int M, int Nout, int K) {
     return p;
 }
 
-template <typename T>
-int launch_dw(const void* dy, const void* x, float* dw, float* db, void* ws, int M, int Nout, int K, hipStream_t st) {
-    using L = DwLay<T>;
-    DwPlan p = plan(M, Nout, K);
-    float* part = reinterpret_cast<float*>(ws);
-    float* bpart = part + (int64_t)p.nslice * Nout * K;
-    size_t lds = 4 * (size_t)L::TILE * sizeof(T);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(linear_dw_kernel<T>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
+enum DwTier { DW_F32, DW_TR, DW_DMA };
+
+// The tier (>= 0) that serves a call, or the GF_ERR_* (< 0) that rejects it.
+int select_kernel(int dtype, int Nout, int K, bool two_source) {
+    const bool dma = dtype == GF_BF16 && Nout % 128 == 0 && K % 128 == 0;
+    if (two_source) return dma ? DW_DMA : GF_ERR_UNSUPPORTED;     // only the DMA tier picks its X source per k-tile
+    const int align = dtype == GF_BF16 ? 8 : 4;                   // 16-byte rows
+    if (Nout % align || K % align) return GF_ERR_ALIGN;
+    if (dtype == GF_F32) return DW_F32;
+    if (dtype != GF_BF16) return GF_ERR_DTYPE;
+    return dma ? DW_DMA : DW_TR;
+}
+
+hipError_t allow_lds(const void* kernel, int bytes) {            // every tier asks for more than the 48 KiB default
+    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
+// plan -> carve the workspace -> tile kernel of `tier` -> slice reduction.  x2 / K1: the second source (DMA tier) or null / 0.
+int launch(DwTier tier, const void* dy, const void* x, const void* x2, int K1, float* dw, float* db, void* ws,
+           int M, int Nout, int K, hipStream_t st) {
+    const DwPlan p = plan(M, Nout, K);
+    const int64_t nw = (int64_t)Nout * K;
+    float* part = reinterpret_cast<float*>(ws);                   // [nslice][Nout][K]
+    float* bpart = part + p.nslice * nw;                          // [nslice][Nout]
+    const dim3 grid(p.ntile * ((p.nslice + 7) / 8) * 8);          // slices padded to the 8 XCDs dw_tile() deals them to
+    const bf16_t *dyh = reinterpret_cast<const bf16_t*>(dy), *xh = reinterpret_cast<const bf16_t*>(x);
+    hipError_t e;
+    switch (tier) {
+    case DW_F32:
+        if ((e = allow_lds(reinterpret_cast<const void*>(linear_dw_f32_kernel), F32_LDS)) != hipSuccess) return (int)e;
+        linear_dw_f32_kernel<<<grid, 256, F32_LDS, st>>>(reinterpret_cast<const float*>(dy), reinterpret_cast<const float*>(x),
+                                                         part, bpart, M, Nout, K, p.rows);
+        break;
+    case DW_TR:
+        if ((e = allow_lds(reinterpret_cast<const void*>(linear_dw_tr_kernel), TR_LDS)) != hipSuccess) return (int)e;
+        linear_dw_tr_kernel<<<grid, 256, TR_LDS, st>>>(dyh, xh, part, bpart, M, Nout, K, p.rows);
+        break;
+    case DW_DMA:
+        if ((e = allow_lds(reinterpret_cast<const void*>(linear_dw_dma_kernel), DM_LDS)) != hipSuccess) return (int)e;
+        linear_dw_dma_kernel<<<grid, 256, DM_LDS, st>>>(dyh, xh, reinterpret_cast<const bf16_t*>(x2), K1, part, bpart, M, Nout, K,
+                                                        p.rows);
+        break;
     }
-    linear_dw_kernel<T><<<dim3(p.ntile * ((p.nslice + 7) / 8) * 8), 256, lds, st>>>(
-        reinterpret_cast<const T*>(dy), reinterpret_cast<const T*>(x), part, bpart, M, Nout, K, p.rows);
-    int64_t nw = (int64_t)Nout * K;
-    const int nwb = (int)((nw / 4 + 63) / 64), nbb = db ? (Nout / 4 + 63) / 64 : 0;
+    if (int rc = (int)hipGetLastError()) return rc;
+    const int nwb = (int)((nw / 4 + 63) / 64), nbb = db ? (Nout / 4 + 63) / 64 : 0;   // 64 float4 columns per block
     linear_dw_reduce<<<dim3(nwb + nbb), 256, 0, st>>>(part, bpart, dw, db, p.nslice, nw, Nout, nwb);
     return (int)hipGetLastError();
 }
@@ -675,52 +700,19 @@ extern "C" int64_t gf_linear_dw_ws_bytes(int M, int Nout, int K) {
     return ((int64_t)p.nslice * Nout * K + (int64_t)p.nslice * Nout) * 4 + 256;
 }
 
-int launch_dw_tr(const void* dy, const void* x, float* dw, float* db, void* ws, int M, int Nout, int K, hipStream_t st,
-                 const void* x2 = nullptr, int K1 = 0) {
-    DwPlan p = plan(M, Nout, K);
-    float* part = reinterpret_cast<float*>(ws);
-    float* bpart = part + (int64_t)p.nslice * Nout * K;
-    if (Nout % 128 == 0 && K % 128 == 0) {
-        const size_t dlds = (size_t)DM_NSTAGE * DM_STAGE;
-        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(linear_dw_dma_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds);
-        if (e2 != hipSuccess) return (int)e2;
-        linear_dw_dma_kernel<<<dim3(p.ntile * ((p.nslice + 7) / 8) * 8), 256, dlds, st>>>(
-            reinterpret_cast<const bf16_t*>(dy), reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(x2), K1,
-            part, bpart, M, Nout, K, p.rows);
-        if (int e3 = (int)hipGetLastError()) return e3;
-        int64_t nw2 = (int64_t)Nout * K;
-        const int nwb2 = (int)((nw2 / 4 + 63) / 64), nbb2 = db ? (Nout / 4 + 63) / 64 : 0;
-        linear_dw_reduce<<<dim3(nwb2 + nbb2), 256, 0, st>>>(part, bpart, dw, db, p.nslice, nw2, Nout, nwb2);
-        return (int)hipGetLastError();
-    }
-    if (x2 != nullptr) return GF_ERR_UNSUPPORTED;          // (two sources: 128-multiple shapes only, checked by the caller)
-    size_t lds = 4 * (size_t)TR_TILE * sizeof(bf16_t);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(linear_dw_tr_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    linear_dw_tr_kernel<<<dim3(p.ntile * ((p.nslice + 7) / 8) * 8), 256, lds, st>>>(
-        reinterpret_cast<const bf16_t*>(dy), reinterpret_cast<const bf16_t*>(x), part, bpart, M, Nout, K, p.rows);
-    int64_t nw = (int64_t)Nout * K;
-    const int nwb = (int)((nw / 4 + 63) / 64), nbb = db ? (Nout / 4 + 63) / 64 : 0;
-    linear_dw_reduce<<<dim3(nwb + nbb), 256, 0, st>>>(part, bpart, dw, db, p.nslice, nw, Nout, nwb);
-    return (int)hipGetLastError();
-}
-
 extern "C" int gf_linear_dw2(const void* dy, const void* x1, const void* x2, int K1, float* dw, float* db, void* ws,
                              int M, int Nout, int K, int dtype, void* stream) {
     if (M <= 0 || Nout <= 0 || K <= 0 || K1 <= 0 || K1 >= K) return GF_ERR_SHAPE;
-    if (dtype != GF_BF16 || Nout % 128 || K1 % 128 || (K - K1) % 128 || x1 == nullptr || x2 == nullptr) return GF_ERR_UNSUPPORTED;
-    return launch_dw_tr(dy, x1, dw, db, ws, M, Nout, K, reinterpret_cast<hipStream_t>(stream), x2, K1);
+    if (K1 % 128 || x1 == nullptr || x2 == nullptr) return GF_ERR_UNSUPPORTED;      // a k-tile reads ONE source
+    const int tier = select_kernel(dtype, Nout, K, true);
+    if (tier < 0) return tier;
+    return launch((DwTier)tier, dy, x1, x2, K1, dw, db, ws, M, Nout, K, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int gf_linear_dw(const void* dy, const void* x, float* dw, float* db, void* ws,
                             int M, int Nout, int K, int dtype, void* stream) {
     if (M <= 0 || Nout <= 0 || K <= 0) return GF_ERR_SHAPE;
-    const int align = dtype == GF_BF16 ? 8 : 4;
-    if (Nout % align || K % align) return GF_ERR_ALIGN;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_F32) return launch_dw<float>(dy, x, dw, db, ws, M, Nout, K, st);
-    if (dtype == GF_BF16) return launch_dw_tr(dy, x, dw, db, ws, M, Nout, K, st);
-    return GF_ERR_DTYPE;
+    const int tier = select_kernel(dtype, Nout, K, false);
+    if (tier < 0) return tier;
+    return launch((DwTier)tier, dy, x, nullptr, 0, dw, db, ws, M, Nout, K, reinterpret_cast<hipStream_t>(stream));
 }

@@ -194,6 +194,24 @@ def _flat2(t, n):
     return t2 if t2.is_contiguous() else t2.contiguous()
 
 
+def _dw(dy2, x2, nout, k, with_bias, x2b=None, k1=0):
+    """fp32 (dW [nout, k], db [nout] or None) of y = x W^T + b from dy2 [M, nout] and x = x2 [M, k] or, with ``x2b``, the
+    virtual concatenation [x2 (k1 columns) | x2b] in one launch (gf_linear_dw2: the caller checks its shape limits).
+    The only place that allocates for, and calls, the weight-gradient kernels."""
+    L = _lib.load()
+    m = x2.shape[0]
+    ws = torch.empty(int(L.gf_linear_dw_ws_bytes(m, nout, k)), dtype=torch.uint8, device=x2.device)
+    dw32 = torch.empty((nout, k), dtype=torch.float32, device=x2.device)
+    db32 = torch.empty((nout,), dtype=torch.float32, device=x2.device) if with_bias else None
+    if x2b is None:
+        _lib.check(L.gf_linear_dw(_p(dy2), _p(x2), _p(dw32), _p(db32), _p(ws), m, nout, k, _dt(x2), _stream()),
+                   "gf_linear_dw")
+    else:
+        _lib.check(L.gf_linear_dw2(_p(dy2), _p(x2), _p(x2b), k1, _p(dw32), _p(db32), _p(ws), m, nout, k, _dt(x2),
+                                   _stream()), "gf_linear_dw2")
+    return dw32, db32
+
+
 class _Linear(torch.autograd.Function):
     """y = x W^T + b (+ res) (+ rotary epilogue): forward and input-gradient GEMM on gf_gemm (library GEMM only for
     shapes outside its plans), weight / bias gradient (a tiny-output, 1e5-deep reduction) on gf_linear_dw, which
@@ -251,13 +269,7 @@ class _Linear(torch.autograd.Function):
             x2 = x.reshape(-1, k)
             if not x2.is_contiguous():
                 x2 = x2.contiguous()
-            m = x2.shape[0]
-            L = _lib.load()
-            ws = torch.empty(int(L.gf_linear_dw_ws_bytes(m, nout, k)), dtype=torch.uint8, device=x.device)
-            dw32 = torch.empty((nout, k), dtype=torch.float32, device=x.device)
-            db32 = torch.empty((nout,), dtype=torch.float32, device=x.device) if ctx.has_bias else None
-            _lib.check(L.gf_linear_dw(_p(dy2), _p(x2), _p(dw32), _p(db32), _p(ws), m, nout, k, _dt(x2),
-                                      _stream()), "gf_linear_dw")
+            dw32, db32 = _dw(dy2, x2, nout, k, ctx.has_bias)
             dw = dw32.to(ctx.wdtype)
             db = None if db32 is None else db32.to(ctx.bdtype)
         return dx, dw, db, dres, None, None, None, None, None, None
@@ -279,17 +291,6 @@ def linear(x, w, b=None, res=None, rotary_cs=None, rot_n=0, chain=None, chain_la
     if res is None or not res.requires_grad:
         res_chain = None
     return _Linear.apply(x, w, b, res, rotary_cs, rot_n, chain, chain_last, res_chain, out)
-
-
-def _dw(dy2, x2, nout, k, with_bias):
-    L = _lib.load()
-    m = x2.shape[0]
-    ws = torch.empty(int(L.gf_linear_dw_ws_bytes(m, nout, k)), dtype=torch.uint8, device=x2.device)
-    dw32 = torch.empty((nout, k), dtype=torch.float32, device=x2.device)
-    db32 = torch.empty((nout,), dtype=torch.float32, device=x2.device) if with_bias else None
-    _lib.check(L.gf_linear_dw(_p(dy2), _p(x2), _p(dw32), _p(db32), _p(ws), m, nout, k, _dt(x2), _stream()),
-               "gf_linear_dw")
-    return dw32, db32
 
 
 class _LinearCat(torch.autograd.Function):
@@ -336,13 +337,7 @@ class _LinearCat(torch.autograd.Function):
             c = c if c.is_contiguous() else c.contiguous()
             if a.dtype == torch.bfloat16 and nout % 128 == 0 and k1 % 128 == 0 and (k - k1) % 128 == 0:
                 # ONE launch over the virtual concatenation (gf_linear_dw2): dY streamed once, dw comes out whole
-                L = _lib.load()
-                m = a.shape[0]
-                ws = torch.empty(int(L.gf_linear_dw_ws_bytes(m, nout, k)), dtype=torch.uint8, device=a.device)
-                dw32 = torch.empty((nout, k), dtype=torch.float32, device=a.device)
-                db32 = torch.empty((nout,), dtype=torch.float32, device=a.device) if ctx.bdtype is not None else None
-                _lib.check(L.gf_linear_dw2(_p(dy2), _p(a), _p(c), k1, _p(dw32), _p(db32), _p(ws), m, nout, k, _dt(a),
-                                           _stream()), "gf_linear_dw2")
+                dw32, db32 = _dw(dy2, a, nout, k, ctx.bdtype is not None, x2b=c, k1=k1)
                 dw = dw32.to(ctx.wdtype)
             else:
                 dwa, db32 = _dw(dy2, a, nout, k1, ctx.bdtype is not None)

@@ -284,3 +284,36 @@ def test_sinkhorn_host_arithmetic_matches_recorded():
         f = key.split(",")
         return ",".join(f[:3] + ["256"] + f[4:])
     assert any(k.split(",")[3] == "512" and v[0] == 0 and want["plan"][at256(k)][0] == 1 for k, v in want["plan"].items())
+
+
+# M: the train step's token count, every M of test_linear_dw / test_linear_cat_weight_gradient_in_one_launch / the ragged-slice
+# test, and the edges of plan()'s 256-row minimum and 64-row rounding.  (Nout, K): the step's five shapes, every shape those tests
+# reach (the two-source ones whole and per source), 64 tiles (1024 x 1024: one per slot of an XCD) and 80 (more than its slots)
+_DW_M = (1, 64, 255, 256, 257, 300, 777, 1000, 2049, 4096, 4133, 5000, 131072)
+_DW_SHAPES = ((8, 8), (136, 72), (264, 136), (128, 128), (128, 256), (256, 128), (256, 256), (256, 384), (256, 512), (512, 256),
+              (512, 512), (768, 256), (1024, 1024), (1280, 1024))
+_DW_INVALID = ((0, 256, 256), (-1, 256, 256), (1000, 0, 256), (1000, 256, 0), (1000, -8, 256), (1000, 256, -128), (0, 0, 0))
+
+
+def _linear_dw_host_record(L):
+    return {f"{m},{n},{k}": int(L.gf_linear_dw_ws_bytes(m, n, k))
+            for m, n, k in [(m, n, k) for m in _DW_M for n, k in _DW_SHAPES] + list(_DW_INVALID)}
+
+
+def test_linear_dw_workspace_matches_recorded():
+    """gf_linear_dw_ws_bytes (host-only: the slice plan of csrc/linear_dw.hip) against tests/golden/linear_dw_host.json, this
+    library's own output recorded before the weight-gradient translation unit got its one launch path.  Whoever changes the
+    slice plan or the workspace layout on purpose re-records the file (json.dump of _linear_dw_host_record)."""
+    import json
+    from glue_factory_amd import lib
+    got = _linear_dw_host_record(lib.load())
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "linear_dw_host.json")))
+    assert got == want
+    assert all(want[f"{m},{n},{k}"] == -2 for m, n, k in _DW_INVALID)                     # GF_ERR_SHAPE
+    assert all(v > 256 for key, v in want.items() if tuple(int(f) for f in key.split(",")) not in _DW_INVALID)
+    # the fixture tells the plan's branches apart: one slice (M below the 256-row minimum), a ragged last slice, the 64-row
+    # rounding (2049 rows for 8 slices: 257 -> 320 rows, 7 slices), slices per XCD clamped to 1 above 64 tiles, and the
+    # step's 512 slots / 4 tiles
+    slices = lambda m, n, k: (want[f"{m},{n},{k}"] - 256) // (4 * (n * k + n))
+    assert slices(255, 256, 256) == 1 and slices(257, 256, 256) == 2 and slices(2049, 1024, 1024) == 7
+    assert slices(131072, 1024, 1024) == 8 == slices(131072, 1280, 1024) and slices(131072, 256, 256) == 128

@@ -447,6 +447,61 @@ def test_linear_dw(dtype, M, Nout, K):
     assert w.grad.dtype == torch.float32 and b.grad.dtype == torch.float32
 
 
+def test_linear_dw_tiers_on_a_ragged_second_slice():
+    """gf_linear_dw / gf_linear_dw2 straight through the C ABI, once per kernel tier of csrc/linear_dw.hip, at M = 300: slices
+    of 256 rows, so the second one has 44 -- a ragged last chunk for the 32-row DMA ring and for the 64-row register-staged
+    kernels alike -- and slices 2 .. 7 of the grid return at once.  dW / db against the fp64 product of the same (rounded)
+    inputs at test_linear_dw's tolerances; db = NULL (no bias blocks in the reduction) gives the same dW and leaves the
+    sentinel where db went before; two calls agree bit for bit; rejected calls return their code and write nothing."""
+    from glue_factory_amd import lib as L_
+    L = L_.load()
+    st = torch.cuda.current_stream().cuda_stream
+    M, SENT = 300, 777.0
+    g = torch.Generator().manual_seed(300)
+
+    def run(dy, xs, dtype_code, with_db, expect=0, out=None, ws=None):
+        nout, k = dy.shape[1], sum(x.shape[1] for x in xs)
+        ws = torch.empty(int(L.gf_linear_dw_ws_bytes(M, nout, k)), dtype=torch.uint8, device=DEV) if ws is None else ws
+        out = torch.full((nout * k + nout,), SENT, device=DEV) if out is None else out        # dW [nout, k] | db [nout]
+        db = out.data_ptr() + 4 * nout * k if with_db else None
+        if len(xs) == 1:
+            rc = L.gf_linear_dw(dy.data_ptr(), xs[0].data_ptr(), out.data_ptr(), db, ws.data_ptr(), M, nout, k, dtype_code, st)
+        else:
+            rc = L.gf_linear_dw2(dy.data_ptr(), xs[0].data_ptr(), xs[1].data_ptr(), xs[0].shape[1], out.data_ptr(), db,
+                                 ws.data_ptr(), M, nout, k, dtype_code, st)
+        assert rc == expect
+        return out[:nout * k].view(nout, k), out[nout * k:nout * k + nout]
+
+    for dtype, nout, ks in ((torch.float32, 136, (72,)),              # register-staged, transposing stores
+                            (torch.bfloat16, 136, (72,)),             # register-staged, transposing reads
+                            (torch.bfloat16, 128, (256,)),            # LDS-DMA ring
+                            (torch.bfloat16, 128, (128, 128))):       # LDS-DMA ring, two sources
+        code = 0 if dtype == torch.float32 else 1
+        dy = torch.randn(M, nout, generator=g).to(DEV, dtype)
+        xs = [torch.randn(M, k, generator=g).to(DEV, dtype) for k in ks]
+        ref_w = dy.double().t() @ torch.cat(xs, 1).double()
+        ref_b = dy.double().sum(0)
+        dw, db = run(dy, xs, code, True)
+        tol = 1e-4 if dtype == torch.float32 else 2e-2
+        for name, a, r in (("dw", dw, ref_w), ("db", db, ref_b)):
+            sc = r.abs().max().item()
+            torch.testing.assert_close(a.double() / sc, r / sc, rtol=tol, atol=tol, msg=lambda m: f"{dtype} {nout} {ks} {name}: {m}")
+        dw_again, db_again = run(dy, xs, code, True)
+        assert torch.equal(dw_again, dw) and torch.equal(db_again, db)
+        dw_nodb, no_db = run(dy, xs, code, False)
+        assert torch.equal(dw_nodb, dw) and bool((no_db == SENT).all())
+
+    z = torch.zeros(M * 256, device=DEV)                                # large enough for every operand below, in any dtype
+    out = torch.full((136 * 256 + 136,), SENT, device=DEV)
+    ws = torch.full((int(L.gf_linear_dw_ws_bytes(M, 136, 256)),), 0x5a, dtype=torch.uint8, device=DEV)
+    as_ = lambda cols: z[:M * cols].view(M, cols)                       # noqa: E731
+    run(as_(136), [as_(128), as_(128)], 1, True, expect=-1, out=out, ws=ws)       # GF_ERR_UNSUPPORTED: two sources, Nout % 128
+    run(as_(136), [as_(68)], 1, True, expect=-3, out=out, ws=ws)                  # GF_ERR_ALIGN: bf16 rows of K % 8 != 0
+    run(as_(136), [as_(72)], 7, True, expect=-4, out=out, ws=ws)                  # GF_ERR_DTYPE
+    torch.cuda.synchronize()
+    assert bool((out == SENT).all()) and bool((ws == 0x5a).all())                 # nothing was launched
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("M,C,relu", [(1000, 512, True), (333, 32, True), (4096, 256, False)])
 def test_batch_norm_act(dtype, M, C, relu):
