@@ -22,7 +22,7 @@ from ._linear import (LIBRARY_GEMMS, GradChain, colsum, gemm, gemm_takes, linear
                       small_linear)
 from ._nll import _SPARSE_SUMS, _known_sums, nll_positive_terms, nll_terms
 from ._assignment import (_head_bwd, assign_write, bgemm, dual_lse, dual_lse_stacked, filter_matches, lg_layer_loss,
-                          rows_argmax, rows_lse)
+                          n_pair_loss, nn_filter, rows_argmax, rows_lse, rows_top2, similarity)
 from ._sinkhorn import sinkhorn, sinkhorn_schedule
 from ._batchnorm import (COLLECTIVES, _BatchNormActSetsSync, _ReplayRunningStats, batch_norm_act, batch_norm_act_sets,
                          replay_running_stats)

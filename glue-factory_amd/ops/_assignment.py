@@ -1,4 +1,5 @@
-"""Assignment head and per-layer loss (csrc/assignment.hip, head_bwd.hip, lg_loss.hip, bgemm.hip)."""
+"""Assignment head, per-layer loss and nearest-neighbour matching (csrc/assignment.hip, head_bwd.hip, lg_loss.hip, bgemm.hip,
+nn_match.hip)."""
 import torch
 
 from .. import lib as _lib
@@ -297,3 +298,113 @@ def filter_matches(max0, arg0, arg1, th):
     _lib.check(_lib.load().gf_filter_matches(_p(max0), _p(arg0), _p(arg1), float(th), _p(m0), _p(m1),
                                              _p(s0), _p(s1), B, M, N, _stream()), "gf_filter_matches")
     return m0, m1, s0, s1
+
+
+# ------------------------------------------------------------------------------ nearest-neighbour matcher (csrc/nn_match.hip)
+@torch.no_grad()
+def rows_top2(a, b):
+    """(best, arg, second) of every row of a b^T without the [B,M,N] tensor -> ([B,M] float, [B,M] int64, [B,M] float).
+    `second` is the second element of the row as a multiset (a duplicated maximum gives second == best); the lowest index
+    wins a tie."""
+    _chk(a, b)
+    a, b = _mat3(a), _mat3(b)
+    assert a.dtype == b.dtype and a.shape[0] == b.shape[0] and a.shape[2] == b.shape[2]
+    B, M, D = a.shape
+    N = b.shape[1]
+    best = torch.empty((B, M), dtype=torch.float32, device=a.device)
+    arg = torch.empty((B, M), dtype=torch.int64, device=a.device)
+    second = torch.empty((B, M), dtype=torch.float32, device=a.device)
+    _lib.check(_lib.load().gf_rows_top2(_p(a), _p(b), _p(best), _p(arg), _p(second), B, M, N, D, _dt(a), _stream()),
+               "gf_rows_top2")
+    return best, arg, second
+
+
+@torch.no_grad()
+def nn_filter(top0, top1, ratio_thresh=None, distance_thresh=None, mutual=True):
+    """find_nn's ratio / distance thresholds and mutual_check on the rows_top2 triples of both directions
+    -> (m0, m1, s0, s1); a falsy threshold is "not set", as in the reference."""
+    best0, arg0, sec0 = (t.contiguous() for t in top0)
+    best1, arg1, sec1 = (t.contiguous() for t in top1)
+    _chk(best0, arg0, sec0, best1, arg1, sec1)
+    B, M = arg0.shape
+    N = arg1.shape[1]
+    dev = arg0.device
+    m0 = torch.empty((B, M), dtype=torch.int64, device=dev)
+    m1 = torch.empty((B, N), dtype=torch.int64, device=dev)
+    s0 = torch.empty((B, M), dtype=torch.float32, device=dev)
+    s1 = torch.empty((B, N), dtype=torch.float32, device=dev)
+    r2 = float(ratio_thresh) ** 2 if ratio_thresh else -1.0
+    d2 = float(distance_thresh) ** 2 if distance_thresh else -1.0
+    _lib.check(_lib.load().gf_nn_filter(_p(best0), _p(arg0), _p(sec0), _p(best1), _p(arg1), _p(sec1), r2, d2,
+                                        int(bool(mutual)), _p(m0), _p(m1), _p(s0), _p(s1), B, M, N, _stream()),
+               "gf_nn_filter")
+    return m0, m1, s0, s1
+
+
+class _Similarity(torch.autograd.Function):
+    """sim = a b^T [B,M,N] in the operands' dtype; backward da = dsim b, db = dsim^T a (all three through gf_bgemm)."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        a, b = _mat3(a), _mat3(b)
+        ctx.save_for_backward(a, b)
+        return bgemm(a, b.transpose(1, 2))
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        g = g.to(a.dtype, memory_format=torch.contiguous_format)
+        da = bgemm(g, b) if ctx.needs_input_grad[0] else None
+        db = bgemm(g.transpose(1, 2), a) if ctx.needs_input_grad[1] else None
+        return da, db
+
+
+def similarity(a, b):
+    return _Similarity.apply(a, b)
+
+
+class _NPairLoss(torch.autograd.Function):
+    """(nll [B], num [B]) of the N-pair loss on a dense similarity with the positives (pb, pi, pj) (pj < 0 = padding):
+    nll = -sum_pos (2 score - lse_row - lse_col) / (2 num), num = max(#positives, 1), score = T (2 - sqrt(max(2 (1 - sim),
+    1e-6))).  The backward writes dsim dense in one pass and reduces dT on the device."""
+
+    @staticmethod
+    def forward(ctx, sim, temperature, pb, pi, pj):
+        _chk(sim, temperature, pb, pi, pj)
+        s = sim.detach().float().contiguous()
+        t = temperature.detach().float().reshape(1)
+        pb, pi, pj = (x.long().contiguous() for x in (pb, pi, pj))
+        B, M, N = s.shape
+        P = pb.shape[0]
+        dev = s.device
+        lse_row = torch.empty((B, M), dtype=torch.float32, device=dev)
+        lse_col = torch.empty((B, N), dtype=torch.float32, device=dev)
+        acc = torch.empty((2, B), dtype=torch.float32, device=dev)
+        cnt_row = torch.empty((B, M), dtype=torch.float32, device=dev)
+        cnt_col = torch.empty((B, N), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().gf_npair_fwd(_p(s), _p(t), _p(pb), _p(pi), _p(pj), P, _p(lse_row), _p(lse_col), _p(acc[0]),
+                                            _p(acc[1]), _p(cnt_row), _p(cnt_col), B, M, N, _stream()), "gf_npair_fwd")
+        num = acc[1].clamp(min=1.0)
+        ctx.save_for_backward(s, t, lse_row, lse_col, cnt_row, cnt_col, num, pb, pi, pj)
+        ctx.meta = (sim.dtype, temperature.dtype, temperature.shape)
+        ctx.mark_non_differentiable(num)
+        return -acc[0] / (2.0 * num), num
+
+    @staticmethod
+    def backward(ctx, g, _gnum):
+        s, t, lse_row, lse_col, cnt_row, cnt_col, num, pb, pi, pj = ctx.saved_tensors
+        B, M, N = s.shape
+        coef = (g.float() / (2.0 * num)).contiguous()
+        dsim = torch.empty_like(s)
+        dT = torch.empty((1,), dtype=torch.float32, device=s.device)
+        _lib.check(_lib.load().gf_npair_bwd(_p(s), _p(t), _p(lse_row), _p(lse_col), _p(cnt_row), _p(cnt_col), _p(coef),
+                                            _p(pb), _p(pi), _p(pj), pb.shape[0], _p(dsim), _p(dT), B, M, N, _stream()),
+                   "gf_npair_bwd")
+        sdt, tdt, tshape = ctx.meta
+        return dsim.to(sdt), dT.reshape(tshape).to(tdt), None, None, None
+
+
+def n_pair_loss(sim, temperature, pos):
+    """-> (nll [B], num [B]) for sim [B,M,N], a scalar temperature tensor and pos = (b, i, j) index vectors (j < 0 is
+    padding).  A (b, i, j) listed k times is a positive of weight k, in the loss, in num and in both gradients."""
+    return _NPairLoss.apply(sim, temperature, *pos)

@@ -37,7 +37,7 @@ extern "C" {
 #define GF_ERR_DTYPE (-4)
 
 /* ABI version; bumped on any signature or workspace-size change (2: gf_attn_bwd's delta workspace doubled; 3: line head + gf_bgemm; 4: smallops; 5: gf_attn_bwd_acc; 9: cast entries with leading dimensions, gf_fold_linear_*, double betas in gf_multi_adam; 10: gf_attn_fwd_ex / GF_ATTN_SPLIT, gf_topk_candidates; 14: gf_sinkhorn_* take `schedule`, gf_sinkhorn_mode removed, gf_probe_hold_cus, gf_linear_dw2, gf_gemm_res2, gf_rowdot2_*; gf_rowdot_fwd / gf_rotary_qk_bwd take a device bias / a base sum; 16: the test diagnostic gf_probe_hold_cus left the product ABI for tests/csrc/gf_test_probe.hip; 17: gf_conv3x3_c64_ld). */
-#define GF_AMD_ABI_VERSION 17
+#define GF_AMD_ABI_VERSION 18
 int gf_abi_version(void);
 
 /* ---- multi-head attention over keypoints --------------------------------------------------
@@ -177,6 +177,44 @@ int gf_head_bwd(const void* a, const void* b, const float* r, const float* c, co
 int gf_filter_matches(const float* max0, const int64_t* arg0, const int64_t* arg1, float th,
                       int64_t* m0, int64_t* m1, float* s0, float* s1,
                       int B, int M, int N, void* stream);
+
+/* ---- nearest-neighbour matcher (gluefactory/models/matchers/nearest_neighbor_matcher.py; csrc/nn_match.hip) --------
+ * gf_rows_top2: for every row i of a [B,M,D], over the rows j < N of b [B,N,D] (S = a b^T, never materialised):
+ *   best[b,i] = max_j S_ij, arg[b,i] = its index (lowest index on ties), second[b,i] = the second element of the row
+ *   taken as a multiset (a duplicated maximum gives second == best; N == 1 gives -inf).
+ * This is `sim.topk(2, dim=-1)` of nearest_neighbor_matcher.py:17 on the einsum of :53; called with (b, a) it serves
+ * `sim.transpose(1, 2)` of :55-57.  fp32 (exact-fp32 MFMA) and bf16 operands, D in {64, 128, 256} (GF_ERR_UNSUPPORTED
+ * otherwise), rows contiguous; best / second fp32, arg int64. */
+int gf_rows_top2(const void* a, const void* b, float* best, int64_t* arg, float* second,
+                 int B, int M, int N, int D, int dtype, void* stream);
+
+/* gf_nn_filter: find_nn's thresholds and mutual_check (nearest_neighbor_matcher.py:18-25, :28-35, :58-59, :63-64) on
+ * the top-2 vectors of both directions (side 0: [B,M], side 1: [B,N]).  With dist = 2 (1 - sim) in fp32 a row keeps its
+ * arg-max when dist_best <= ratio2 * dist_second (ratio2 = ratio_thresh^2; < 0: not set) and dist_best <= dist2
+ * (dist2 = distance_thresh^2; < 0: not set); with mutual != 0 the match must also be its partner's thresholded match.
+ * m0 [B,M], m1 [B,N] int64 (-1 = unmatched); s0, s1 fp32 (1.0 where matched, else 0.0). */
+int gf_nn_filter(const float* best0, const int64_t* arg0, const float* second0,
+                 const float* best1, const int64_t* arg1, const float* second1,
+                 float ratio2, float dist2, int mutual,
+                 int64_t* m0, int64_t* m1, float* s0, float* s1, int B, int M, int N, void* stream);
+
+/* N-pair loss on a dense similarity sim [B,M,N] fp32 (nearest_neighbor_matcher.py:76-93) with the temperature read from
+ * device memory (no host copy of the parameter): score = T (2 - sqrt(max(2 (1 - sim), 1e-6))).
+ * gf_npair_fwd: lse_row [B,M] = LSE_j score, lse_col [B,N] = LSE_i score (the normalisers of :83-84), and over the
+ *   positives (pb, pi, pj)[P] of gt_assignment (pj < 0: padding entry, skipped):
+ *   acc[b] = sum_pos (2 score_ij - lse_row_i - lse_col_j)  (= the two sums of :88-89 before the division),
+ *   cnt[b] = number of positives, cnt_row [B,M] / cnt_col [B,N] = positives per row / column (fp32 atomics).
+ * gf_npair_bwd: autograd of :80-90 for nll_b = -acc_b / (2 num_b): with coef[b] = dL/dnll_b / (2 num_b),
+ *   dscore = coef (cnt_row softmax_row + cnt_col softmax_col - 2 A),  dsim = dscore T / sqrt(2 (1 - sim)) where the
+ *   clamp is inactive and 0 where it is active, dT[0] = sum dscore (2 - sqrt(.)).  Every (b, i, j) appears at most once
+ *   in the positive list.  B M N < 2^31 (GF_ERR_UNSUPPORTED otherwise). */
+int gf_npair_fwd(const float* sim, const float* temperature, const int64_t* pb, const int64_t* pi,
+                 const int64_t* pj, int64_t P, float* lse_row, float* lse_col, float* acc, float* cnt,
+                 float* cnt_row, float* cnt_col, int B, int M, int N, void* stream);
+int gf_npair_bwd(const float* sim, const float* temperature, const float* lse_row, const float* lse_col,
+                 const float* cnt_row, const float* cnt_col, const float* coef, const int64_t* pb,
+                 const int64_t* pi, const int64_t* pj, int64_t P, float* dsim, float* dT,
+                 int B, int M, int N, void* stream);
 
 /* ---- log-domain Sinkhorn optimal transport (gluefactory_nonfree/superglue.py:186-214) --------
  * Z [B, M+1, N+1] fp32 couplings (scores augmented with the bin score), iterated `iters`
