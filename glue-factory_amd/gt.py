@@ -212,10 +212,66 @@ def gt_matches_from_pose_depth(kp0, kp1, data, pos_th=3, neg_th=5, epi_th=None, 
             "proj_0to1": kp0_1, "proj_1to0": kp1_0, "visible0": visible0, "visible1": visible1}
 
 
+def _mm3(A, B):
+    """[..., 3, 3] x [..., 3, 3] as broadcast multiply-adds (as warp_points: exact fp32 in any autocast state, elementwise
+    kernels only)."""
+    return A[..., :, 0:1] * B[..., 0:1, :] + A[..., :, 1:2] * B[..., 1:2, :] + A[..., :, 2:3] * B[..., 2:3, :]
+
+
+def fundamental_matrix(camera0, camera1, T_0to1):
+    """F = K1^-T [t]x R K0^-1 (gluefactory/geometry/gt_generation.py:77-81), fp32 [..., 3, 3], maps a point of image 0 to its
+    line in image 1.  The inverses go through inv3x3 and the products through _mm3: no library solver, no host read, so
+    the construction can be captured in a hipGraph."""
+    from .geometry import skew_symmetric
+    K0i, K1i = inv3x3(camera0.calibration_matrix().float()), inv3x3(camera1.calibration_matrix().float())
+    E = _mm3(skew_symmetric(T_0to1.t.float()), T_0to1.R.float())
+    return _mm3(_mm3(K1i.transpose(-1, -2), E), K0i)
+
+
+def _flag_ptr(flag):
+    assert flag is None or (flag.dtype == torch.bool and flag.is_contiguous() and flag.is_cuda)
+    return None if flag is None else flag.data_ptr()
+
+
+def epi_min(own, oth, Fm, own_flag=None, oth_flag=None):
+    """gf_gt_epi_min: per own point [B,No,2] the minimum symmetric epipolar distance to the flagged points of oth [B,Ns,2]
+    (bool flags, None = all); Fm [B,3,3] maps own points to lines in the other image.  +inf where nothing is flagged."""
+    from . import lib as _lib
+    b, no = own.shape[:2]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda for t in (own, oth, Fm))
+    assert oth.shape[0] == b and Fm.shape == (b, 3, 3)
+    assert own_flag is None or own_flag.shape == (b, no)
+    assert oth_flag is None or oth_flag.shape == (b, oth.shape[1])
+    out = torch.empty((b, no), dtype=torch.float32, device=own.device)
+    _lib.check(_lib.load().gf_gt_epi_min(own.data_ptr(), oth.data_ptr(), Fm.data_ptr(), _flag_ptr(own_flag),
+                                         _flag_ptr(oth_flag), out.data_ptr(), b, no, oth.shape[1],
+                                         torch.cuda.current_stream().cuda_stream), "gf_gt_epi_min")
+    return out
+
+
+def depth_reward(kp0, kp0_1, kp1, kp1_0, visible0, visible1, Fm, pos_th, neg_th, flag0=None, flag1=None):
+    """gf_gt_depth_reward: reward [B,M,N] = (dist < pos_th^2) - (epi > neg_th) in one pass (see include/gf_amd.h)."""
+    from . import lib as _lib
+    b, m = kp0.shape[:2]
+    n = kp1.shape[1]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda for t in (kp0, kp0_1, kp1, kp1_0, Fm))
+    assert kp0_1.shape == kp0.shape == (b, m, 2) and kp1_0.shape == kp1.shape == (b, n, 2) and Fm.shape == (b, 3, 3)
+    assert visible0.shape == (b, m) and visible1.shape == (b, n)
+    assert (flag0 is None) == (flag1 is None)
+    assert flag0 is None or (flag0.shape == (b, m) and flag1.shape == (b, n))
+    reward = torch.empty((b, m, n), dtype=torch.float32, device=kp0.device)
+    _lib.check(_lib.load().gf_gt_depth_reward(kp0.data_ptr(), kp0_1.data_ptr(), kp1.data_ptr(), kp1_0.data_ptr(),
+                                              _flag_ptr(visible0), _flag_ptr(visible1), Fm.data_ptr(), _flag_ptr(flag0),
+                                              _flag_ptr(flag1), reward.data_ptr(), float(pos_th) ** 2, float(neg_th), b, m, n,
+                                              torch.cuda.current_stream().cuda_stream), "gf_gt_depth_reward")
+    return reward
+
+
 @torch.no_grad()
-def gt_matches_from_pose_depth_fused(kp0, kp1, data, pos_th=3, neg_th=5, cc_th=None, **kw):
-    """Same labels without any [B,M,N] fp32 tensor (HIP nearest-neighbour kernel gf_gt_nn); for the
-    configuration the matchers train with (no epipolar extension, no dense ``reward``).  Points that are not
+def gt_matches_from_pose_depth_fused(kp0, kp1, data, pos_th=3, neg_th=5, cc_th=None, epi_th=None, with_reward=False, **kw):
+    """Same labels without any [B,M,N] fp32 intermediate: the HIP nearest-neighbour kernel gf_gt_nn, gf_gt_epi_min for the
+    epipolar extension of the negatives (``epi_th``: as in the reference it only switches the extension on, the distance is
+    compared with ``neg_th``) and gf_gt_depth_reward for the dense ``reward`` (only on request).  Points that are not
     co-visible are moved far away for the mutual-NN search (their rows / columns would be +inf in the dense
     form); the negative test runs on the true reprojections, exactly as in the dense form."""
     from . import lib as _lib
@@ -260,11 +316,28 @@ def gt_matches_from_pose_depth_fused(kp0, kp1, data, pos_th=3, neg_th=5, cc_th=N
     m1 = torch.where(pos1, min1, torch.full_like(min1, IGNORE_FEATURE))
     m0 = torch.where((own0 > neg_th ** 2) & valid0, torch.full_like(m0, UNMATCHED_FEATURE), m0)
     m1 = torch.where((own1 > neg_th ** 2) & valid1, torch.full_like(m1, UNMATCHED_FEATURE), m1)
-    return {"assignment": positive, "assignment_col0": torch.where(pos0, min0, torch.full_like(min0, -1)),
-            "matches0": m0, "matches1": m1,
-            "matching_scores0": (m0 > -1).float(), "matching_scores1": (m1 > -1).float(),
-            "depth_keypoints0": d0, "depth_keypoints1": d1,
-            "proj_0to1": kp0_1, "proj_1to0": kp1_0, "visible0": visible0, "visible1": visible1}
+    reward = flag0 = flag1 = None
+    if epi_th is not None or with_reward:
+        Fm = fundamental_matrix(data["view0"]["camera"], data["view1"]["camera"], data["T_0to1"]).expand(b, 3, 3).contiguous()
+    if epi_th is not None:
+        # more negatives: points without depth whose epipolar line passes no ignored point of the other view
+        flag0, flag1 = m0 == IGNORE_FEATURE, m1 == IGNORE_FEATURE
+        emin0 = epi_min(kp0f, kp1f, Fm, flag0, flag1)
+        emin1 = epi_min(kp1f, kp0f, Fm.transpose(-1, -2).contiguous(), flag1, flag0)
+        m0 = torch.where(~valid0 & (emin0 > neg_th), torch.full_like(m0, UNMATCHED_FEATURE), m0)
+        m1 = torch.where(~valid1 & (emin1 > neg_th), torch.full_like(m1, UNMATCHED_FEATURE), m1)
+    if with_reward:
+        # with epi_th the reference builds the reward from the MASKED epipolar distance (flags of before the extension)
+        reward = depth_reward(kp0f, p01, kp1f, p10, visible0.contiguous(), visible1.contiguous(), Fm, pos_th, neg_th,
+                              flag0, flag1)
+    out = {"assignment": positive, "assignment_col0": torch.where(pos0, min0, torch.full_like(min0, -1)),
+           "matches0": m0, "matches1": m1,
+           "matching_scores0": (m0 > -1).float(), "matching_scores1": (m1 > -1).float(),
+           "depth_keypoints0": d0, "depth_keypoints1": d1,
+           "proj_0to1": kp0_1, "proj_1to0": kp1_0, "visible0": visible0, "visible1": visible1}
+    if with_reward:
+        out["reward"] = reward
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ lines

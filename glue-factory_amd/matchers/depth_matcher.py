@@ -1,5 +1,6 @@
 """Ground-truth "matcher" from depth + relative pose, mirroring gluefactory/models/matchers/depth_matcher.py:16-89
-(keys, defaults, outputs).  Points: the fused HIP nearest-neighbour kernel (gf_gt_nn) where its preconditions hold.  Lines
+(keys, defaults, outputs).  Points on the GPU: the fused HIP kernels (gf_gt_nn; gf_gt_epi_min with `th_epi`; gf_gt_depth_reward
+with `with_reward`), no [B,M,N] fp32 intermediate; CPU tensors and empty keypoint sets take the dense torch form.  Lines
 (`use_lines`): gt.gt_line_matches_from_pose_depth -- torch ops on the keypoints' device + the Hungarian assignment on the
 CPU (scipy), exactly as gt_generation.py:207-407 does it."""
 import torch
@@ -46,9 +47,10 @@ class DepthMatcher(BaseModel):
         kw = {k: data[k] for k in keys} if "depth_keypoints0" in data else {}
         kp0, kp1 = data["keypoints0"].float(), data["keypoints1"].float()
         with torch.autocast(device_type=kp0.device.type, enabled=False):
-            if kp0.is_cuda and self.conf.th_epi is None and not self.conf.with_reward and kp0.shape[1] and kp1.shape[1]:
+            if kp0.is_cuda and kp0.shape[1] and kp1.shape[1]:
                 return gt_matches_from_pose_depth_fused(kp0, kp1, data, pos_th=self.conf.th_positive,
-                                                        neg_th=self.conf.th_negative, cc_th=self.conf.th_consistency, **kw)
+                                                        neg_th=self.conf.th_negative, cc_th=self.conf.th_consistency,
+                                                        epi_th=self.conf.th_epi, with_reward=self.conf.with_reward, **kw)
             return gt_matches_from_pose_depth(kp0, kp1, data, pos_th=self.conf.th_positive, neg_th=self.conf.th_negative,
                                               epi_th=self.conf.th_epi, cc_th=self.conf.th_consistency, **kw)
 

@@ -36,8 +36,8 @@ extern "C" {
 #define GF_ERR_ALIGN (-3)
 #define GF_ERR_DTYPE (-4)
 
-/* ABI version; bumped on any signature or workspace-size change (2: gf_attn_bwd's delta workspace doubled; 3: line head + gf_bgemm; 4: smallops; 5: gf_attn_bwd_acc; 9: cast entries with leading dimensions, gf_fold_linear_*, double betas in gf_multi_adam; 10: gf_attn_fwd_ex / GF_ATTN_SPLIT, gf_topk_candidates; 14: gf_sinkhorn_* take `schedule`, gf_sinkhorn_mode removed, gf_probe_hold_cus, gf_linear_dw2, gf_gemm_res2, gf_rowdot2_*; gf_rowdot_fwd / gf_rotary_qk_bwd take a device bias / a base sum; 16: the test diagnostic gf_probe_hold_cus left the product ABI for tests/csrc/gf_test_probe.hip; 17: gf_conv3x3_c64_ld). */
-#define GF_AMD_ABI_VERSION 18
+/* ABI version; bumped on any signature or workspace-size change (2: gf_attn_bwd's delta workspace doubled; 3: line head + gf_bgemm; 4: smallops; 5: gf_attn_bwd_acc; 9: cast entries with leading dimensions, gf_fold_linear_*, double betas in gf_multi_adam; 10: gf_attn_fwd_ex / GF_ATTN_SPLIT, gf_topk_candidates; 14: gf_sinkhorn_* take `schedule`, gf_sinkhorn_mode removed, gf_probe_hold_cus, gf_linear_dw2, gf_gemm_res2, gf_rowdot2_*; gf_rowdot_fwd / gf_rotary_qk_bwd take a device bias / a base sum; 16: the test diagnostic gf_probe_hold_cus left the product ABI for tests/csrc/gf_test_probe.hip; 17: gf_conv3x3_c64_ld; 19: gf_gt_epi_min, gf_gt_depth_reward). */
+#define GF_AMD_ABI_VERSION 19
 int gf_abi_version(void);
 
 /* ---- multi-head attention over keypoints --------------------------------------------------
@@ -436,6 +436,27 @@ int gf_bn_replay_running(const float* mvr, int sets, int C, float n, float momen
  * labelling needs (mutual arg-mins, positive / negative thresholds) without any [B,M,N] tensor. */
 int gf_gt_nn(const float* own, const float* own_warped, const float* oth, const float* oth_warped,
              int64_t* arg, float* dmin, float* own_min, int B, int No, int Ns, void* stream);
+
+/* ---- epipolar part of the depth ground truth (gluefactory/geometry/gt_generation.py:77-91,95;
+ * gluefactory/geometry/epipolar.py:59-72 sym_epipolar_distance_all), without any [B,M,N] intermediate.
+ * F [B,9] (row-major 3x3) maps a point of the "own" image to its line in the "other" image.  For an own point (x, y) and
+ * another point p:  l = F (x, y, 1), na = sqrt(l0^2 + l1^2 + 1e-15), nb = sqrt((F^T p)0^2 + (F^T p)1^2 + 1e-15),
+ *   epi = (|p . l| / na + |p . l| / nb) / 2      (true division and sqrtf).
+ * gf_gt_epi_min: out_min[b,i] = min over the flagged other points j of epi(i, j); +inf for an unflagged own point or when no
+ *   other point is flagged (gt_generation.py:86-89: where(mask_ignore, epi_dist, inf).min()).  own [B,No,2], oth [B,Ns,2];
+ *   own_flag [B,No], oth_flag [B,Ns] one byte per point, non-zero = set, NULL = all set.  The second direction is the same
+ *   call with the two sets swapped and F^T.
+ * gf_gt_depth_reward: reward[b,i,j] = (dist < pos_th2) - (epi > neg_th), [B,M,N] fp32 (gt_generation.py:95), with
+ *   dist = max(|kp0_1[i] - kp1[j]|^2, |kp0[i] - kp1_0[j]|^2) where vis0[i] and vis1[j] (one byte each; tested first, the
+ *   reprojections kp0_1 / kp1_0 of points without depth may be NaN), +inf elsewhere; epi as above with own = kp0, other =
+ *   kp1, forced to +inf outside flag0[i] & flag1[j] (both nullable: the reward of a call with th_epi is built from the
+ *   masked distance, :87).  pos_th2 is the SQUARED positive threshold (pixels^2), neg_th is in pixels.
+ * Both return GF_ERR_SHAPE when a dimension is <= 0. */
+int gf_gt_epi_min(const float* own, const float* oth, const float* F, const uint8_t* own_flag, const uint8_t* oth_flag,
+                  float* out_min, int B, int No, int Ns, void* stream);
+int gf_gt_depth_reward(const float* kp0, const float* kp0_1, const float* kp1, const float* kp1_0, const uint8_t* vis0,
+                       const uint8_t* vis1, const float* F, const uint8_t* flag0, const uint8_t* flag1, float* reward,
+                       float pos_th2, float neg_th, int B, int M, int N, void* stream);
 
 /* ---- frozen SuperPoint extractor tails (gluefactory/models/extractors/superpoint_open.py; the
  * convolutions stay on the stock library).
