@@ -369,6 +369,47 @@ def _close_point_counts(seg, pts, dist_th, keep=None):
     return close.sum(-1)
 
 
+def _close_point_counts_fused(seg, pts, dist_th, keep=None, transposed=False):
+    """_close_point_counts through the HIP kernel gf_line_close_counts (csrc/gt_lines.hip): the same counts as that function
+    gives on CUDA tensors (fp16 arithmetic, every operation rounded by itself), without the [B,A,C,P] tensors.  The
+    [B,A]-sized prologue (difference, fp16-rounded length, direction) is the same torch code; the kernel takes it from there.
+    seg [B,A,4] fp32, pts [B,C,P,2] fp32, keep [B,C,P] bool or None -> int32 [B,A,C], or [B,C,A] with ``transposed``."""
+    from . import lib as _lib
+    assert all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (seg, pts))
+    b, a = seg.shape[:2]
+    c, npts = pts.shape[1:3]
+    assert seg.shape == (b, a, 4) and pts.shape == (b, c, npts, 2)
+    assert keep is None or keep.shape == (b, c, npts)
+    d = seg[..., 2:] - seg[..., :2]
+    length = torch.norm(d, dim=-1).half()
+    u = (d / length.unsqueeze(-1)).half().contiguous()
+    end = seg[..., 2:].contiguous()
+    count = torch.empty((b, c, a) if transposed else (b, a, c), dtype=torch.int32, device=seg.device)
+    _lib.check(_lib.load().gf_line_close_counts(end.data_ptr(), u.data_ptr(), length.data_ptr(), pts.data_ptr(), _flag_ptr(keep),
+                                                count.data_ptr(), b, a, c, npts, float(dist_th), int(transposed),
+                                                torch.cuda.current_stream().cuda_stream), "gf_line_close_counts")
+    return count
+
+
+def _line_count_pair(l0, l1, p0_in1, p1_in0, dist_th, keep0, keep1, fused):
+    """The two close-point counts of one line ground truth, both as [B,L0,L1]: c0 = samples of view 1's lines on view 0's
+    segments, c1t = samples of view 0's lines on view 1's segments.  ``fused``: None = the HIP kernel on a HIP device (the
+    second count is written transposed by the kernel), False = the torch form, True = the kernel, an error on CPU tensors.
+    A view without lines always takes the torch form: the kernel is never launched on an empty axis."""
+    if fused and not l0.is_cuda:
+        raise RuntimeError("gt line counts: fused=True needs tensors on a HIP device (gf_line_close_counts has no CPU fallback)")
+    if fused is None:
+        fused = l0.is_cuda
+    if not fused or l0.shape[1] == 0 or l1.shape[1] == 0:
+        return _close_point_counts(l0, p1_in0, dist_th, keep1), _close_point_counts(l1, p0_in1, dist_th, keep0).transpose(-1, -2)
+    prep = lambda t: t.float().contiguous()
+    flag = lambda k: None if k is None else k.contiguous()
+    c0 = _close_point_counts_fused(prep(l0), prep(p1_in0), dist_th, flag(keep1))
+    c1t = _close_point_counts_fused(prep(l1), prep(p0_in1), dist_th, flag(keep0), transposed=True)
+    # int64 as the torch form's sum: _assign_lines derives its index tensors from the type of the product of the two
+    return c0.long(), c1t.long()
+
+
 def _line_samples(seg, npts):
     """npts points on every segment, end points included: [B,L,4] -> [B,L,npts,2] (gt_generation.py:164-170)."""
     step = (seg[..., 2:4] - seg[..., :2]) / (npts - 1)
@@ -422,12 +463,14 @@ def _assign_lines(both, mask_close, unmatched0, unmatched1, ignore0, ignore1):
 
 @torch.no_grad()
 def gt_line_matches_from_homography(pred_lines0, pred_lines1, valid_lines0, valid_lines1, shape0, shape1, H,
-                                    npts=50, dist_th=5, overlap_th=0.2, min_visibility_th=0.2):
+                                    npts=50, dist_th=5, overlap_th=0.2, min_visibility_th=0.2, fused=None):
     """Line ground truth under a homography (gluefactory/geometry/gt_generation.py:409-558): sample npts points
     on every segment, warp them, count per segment pair how many warped samples fall on the other segment (both
     ways), keep pairs whose two overlaps exceed overlap_th, solve the one-to-one assignment with the Hungarian
     method on CPU (scipy, as the reference) and label the rest unmatched (-1) / ignored (-2, invalid lines).
-    Returns (assignment [B,L0,L1] bool, matches0 [B,L0], matches1 [B,L1])."""
+    Returns (assignment [B,L0,L1] bool, matches0 [B,L0], matches1 [B,L1]).
+    ``fused``: None counts with the HIP kernel gf_line_close_counts when the lines are on a HIP device and neither view is
+    empty (no [B,L0,L1,npts] tensor), False forces the torch form (_close_point_counts), True raises on CPU tensors."""
     h0, w0 = shape0[-2:]
     h1, w1 = shape1[-2:]
     l0, l1 = _segments(pred_lines0.clone()), _segments(pred_lines1.clone())
@@ -440,8 +483,7 @@ def gt_line_matches_from_homography(pred_lines0, pred_lines1, valid_lines0, vali
     p1_in0 = warp_points(_line_samples(l1, npts).reshape(b, n1 * npts, 2), H, inverse=True).reshape(b, n1, npts, 2)
     out_of0 = _mostly_outside(p1_in0, w0, h0, min_visibility_th)                         # [B,L1]
     out_of1 = _mostly_outside(p0_in1, w1, h1, min_visibility_th)                         # [B,L0]
-    c0 = _close_point_counts(l0, p1_in0, dist_th)            # [B,L0,L1]
-    c1t = _close_point_counts(l1, p0_in1, dist_th).transpose(-1, -2)
+    c0, c1t = _line_count_pair(l0, l1, p0_in1, p1_in0, dist_th, None, None, fused)       # both [B,L0,L1]
     both = c0 * c1t
     mask_close = (c1t > npts * overlap_th) & (c0 > npts * overlap_th) & ~out_of0.unsqueeze(1) & ~out_of1.unsqueeze(-1)
     unmatched0 = torch.all(~mask_close, dim=2) | out_of1
@@ -453,7 +495,7 @@ def gt_line_matches_from_homography(pred_lines0, pred_lines1, valid_lines0, vali
 
 @torch.no_grad()
 def gt_line_matches_from_pose_depth(pred_lines0, pred_lines1, valid_lines0, valid_lines1, data, npts=50, dist_th=5,
-                                    overlap_th=0.2, min_visibility_th=0.5):
+                                    overlap_th=0.2, min_visibility_th=0.5, fused=None):
     """Line ground truth from depth maps and the relative pose (gluefactory/geometry/gt_generation.py:207-407; the line
     branch of depth_matcher.py:70-87): sample npts points on every segment (clamped into its depth map), lift them through
     the sampled depth and reproject into the other view; a pair of segments is close when enough VISIBLE reprojected samples
@@ -462,12 +504,14 @@ def gt_line_matches_from_pose_depth(pred_lines0, pred_lines1, valid_lines0, vali
     flagged invalid, is ignored (-2).  Returns (assignment [B,L0,L1] bool, matches0 [B,L0], matches1 [B,L1]).
     (The reference reads the inverse pose as `data.get(data["T_1to0"], data["T_0to1"].inv())`, i.e. always the inverse of
     T_0to1: so does this.)
-    PARITY IS WITH THE REFERENCE'S CPU PATH (what tests/golden/gt_lines_depth.npz pins bit for bit).  On CUDA the reference
-    additionally rounds the centred samples and the rotation of its perpendicular-distance test to fp16
-    (gt_generation.py:193-195: `.half()` when `is_cuda`), so labels of segment pairs within fp16 rounding (~1e-3 relative) of
-    `dist_th` / of a segment end can differ from a reference run ON A GPU; only the segment length is kept fp16-rounded here, as
-    the reference's CPU path keeps it.  The reference's early return for inputs without elements is covered by the n0 == 0 /
-    n1 == 0 branch below."""
+    On CPU tensors the counts follow the reference's CPU path (what tests/golden/gt_lines_depth.npz pins bit for bit): only
+    the segment length is fp16-rounded.  On CUDA tensors they follow its GPU path: _close_point_counts additionally rounds
+    the centred samples and the direction to fp16 (gt_generation.py:193-195: `.half()` when `is_cuda`) and carries the
+    along / perpendicular arithmetic out in fp16, so labels of segment pairs within fp16 rounding (~1e-3 relative) of
+    `dist_th` / of a segment end can differ between a CPU and a GPU run, as they do in the reference.
+    ``fused``: None counts with the HIP kernel gf_line_close_counts when the lines are on a HIP device (the same fp16
+    arithmetic, no [B,L0,L1,npts] tensor), False forces the torch form, True raises on CPU tensors.  The reference's early
+    return for inputs without elements is covered by the n0 == 0 / n1 == 0 branch below."""
     from .geometry import project, sample_depth
     b, n0, n1 = pred_lines0.shape[0], pred_lines0.shape[1], pred_lines1.shape[1]
     if n0 == 0 or n1 == 0:
@@ -493,8 +537,7 @@ def gt_line_matches_from_pose_depth(pred_lines0, pred_lines1, valid_lines0, vali
     out_of0 = _mostly_outside(p1_in0, w0, h0, min_visibility_th)                         # [B,L1]
     out_of1 = _mostly_outside(p0_in1, w1, h1, min_visibility_th)                         # [B,L0]
     vis0, vis1 = visible0.reshape(b, n0, npts), visible1.reshape(b, n1, npts)
-    c0 = _close_point_counts(l0, p1_in0, dist_th, vis1)                                  # [B,L0,L1]
-    c1t = _close_point_counts(l1, p0_in1, dist_th, vis0).transpose(-1, -2)
+    c0, c1t = _line_count_pair(l0, l1, p0_in1, p1_in0, dist_th, vis0, vis1, fused)       # both [B,L0,L1]
     both = c0 * c1t
     mask_close = (c1t > vis0.float().sum(-1)[:, :, None] * overlap_th) & (c0 > vis1.float().sum(-1)[:, None] * overlap_th)
     unmatched0 = torch.all(~mask_close, dim=2) | out_of1

@@ -1,8 +1,9 @@
 """Ground-truth "matcher" from depth + relative pose, mirroring gluefactory/models/matchers/depth_matcher.py:16-89
 (keys, defaults, outputs).  Points on the GPU: the fused HIP kernels (gf_gt_nn; gf_gt_epi_min with `th_epi`; gf_gt_depth_reward
 with `with_reward`), no [B,M,N] fp32 intermediate; CPU tensors and empty keypoint sets take the dense torch form.  Lines
-(`use_lines`): gt.gt_line_matches_from_pose_depth -- torch ops on the keypoints' device + the Hungarian assignment on the
-CPU (scipy), exactly as gt_generation.py:207-407 does it."""
+(`use_lines`): gt.gt_line_matches_from_pose_depth -- sampling and reprojection with torch ops on the lines' device, the
+close-point counts on a HIP device through the fused kernel gf_line_close_counts (no [B,L0,L1,npts] tensor; torch ops on the
+CPU) + the Hungarian assignment on the CPU (scipy), exactly as gt_generation.py:207-407 does it."""
 import torch
 
 from ..base_model import BaseModel

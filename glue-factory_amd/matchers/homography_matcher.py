@@ -4,8 +4,9 @@ Plugin-surface mirror of gluefactory/models/matchers/homography_matcher.py:8-66 
 same required inputs, same output names.  Points (``use_points``) are labelled by ``glue_factory_amd.gt``
 (restating gluefactory/geometry/gt_generation.py:109-161; on a HIP device through the fused nearest-neighbour
 kernel gf_gt_nn, which never builds a [B,M,N] fp32 tensor).  Lines (``use_lines``) go through
-``gt.gt_line_matches_from_homography`` (gt_generation.py:409-558: torch overlap counts, Hungarian assignment
-on the host with scipy, exactly as the reference does it)."""
+``gt.gt_line_matches_from_homography`` (gt_generation.py:409-558: overlap counts, on a HIP device through the
+fused kernel gf_line_close_counts, which never builds a [B,L0,L1,npts] tensor, and with torch ops on the CPU; Hungarian
+assignment on the host with scipy, exactly as the reference does it)."""
 from .. import gt as _gt
 from ..base_model import BaseModel
 

@@ -36,8 +36,8 @@ extern "C" {
 #define GF_ERR_ALIGN (-3)
 #define GF_ERR_DTYPE (-4)
 
-/* ABI version; bumped on any signature or workspace-size change (2: gf_attn_bwd's delta workspace doubled; 3: line head + gf_bgemm; 4: smallops; 5: gf_attn_bwd_acc; 9: cast entries with leading dimensions, gf_fold_linear_*, double betas in gf_multi_adam; 10: gf_attn_fwd_ex / GF_ATTN_SPLIT, gf_topk_candidates; 14: gf_sinkhorn_* take `schedule`, gf_sinkhorn_mode removed, gf_probe_hold_cus, gf_linear_dw2, gf_gemm_res2, gf_rowdot2_*; gf_rowdot_fwd / gf_rotary_qk_bwd take a device bias / a base sum; 16: the test diagnostic gf_probe_hold_cus left the product ABI for tests/csrc/gf_test_probe.hip; 17: gf_conv3x3_c64_ld; 19: gf_gt_epi_min, gf_gt_depth_reward). */
-#define GF_AMD_ABI_VERSION 19
+/* ABI version; bumped on any signature or workspace-size change (2: gf_attn_bwd's delta workspace doubled; 3: line head + gf_bgemm; 4: smallops; 5: gf_attn_bwd_acc; 9: cast entries with leading dimensions, gf_fold_linear_*, double betas in gf_multi_adam; 10: gf_attn_fwd_ex / GF_ATTN_SPLIT, gf_topk_candidates; 14: gf_sinkhorn_* take `schedule`, gf_sinkhorn_mode removed, gf_probe_hold_cus, gf_linear_dw2, gf_gemm_res2, gf_rowdot2_*; gf_rowdot_fwd / gf_rotary_qk_bwd take a device bias / a base sum; 16: the test diagnostic gf_probe_hold_cus left the product ABI for tests/csrc/gf_test_probe.hip; 17: gf_conv3x3_c64_ld; 19: gf_gt_epi_min, gf_gt_depth_reward; 20: gf_line_close_counts). */
+#define GF_AMD_ABI_VERSION 20
 int gf_abi_version(void);
 
 /* ---- multi-head attention over keypoints --------------------------------------------------
@@ -457,6 +457,21 @@ int gf_gt_epi_min(const float* own, const float* oth, const float* F, const uint
 int gf_gt_depth_reward(const float* kp0, const float* kp0_1, const float* kp1, const float* kp1_0, const uint8_t* vis0,
                        const uint8_t* vis1, const float* F, const uint8_t* flag0, const uint8_t* flag1, float* reward,
                        float pos_th2, float neg_th, int B, int M, int N, void* stream);
+
+/* ---- close-point counts of the line ground truth (gluefactory/geometry/gt_generation.py:173-206 and the `.sum(-1)` over
+ * the sampled points of :296-300 / :470-480), without any [B,A,C,P] intermediate (ABI 20).
+ * count[b,a,c] = number of the P points pts[b,c,:] (of those with keep[b,c,p] != 0 when keep is given; NULL = all) that pass
+ * the test against segment a, in fp16 with every operation rounded by itself, as torch computes it on a CUDA tensor:
+ *   rel = half(pts[b,c,p] - end[b,a])                    (fp32 subtract, one rounding)
+ *   along = half(half(rel.x * dir.x) + half(rel.y * dir.y)),  perp = half(half(rel.y * dir.x) - half(rel.x * dir.y))
+ *   passes = along <= 0 && |along| <= len && |perp| < half(dist_th)
+ * (no fused multiply-add, fp16 subnormals kept, NaN / inf never pass; dist_th is rounded to fp16 before the comparison, as
+ * torch casts a Python scalar to the tensor's type).  end [B,A,2] fp32 = the END point (x1, y1) of every segment; dir [B,A,2]
+ * and len [B,A] are IEEE fp16 bit patterns prepared by the caller: len = half(|d|), dir = half(d / len) with d = end - start.
+ * pts [B,C,P,2] fp32, keep [B,C,P] one byte per point, count int32 [B,A,C], or [B,C,A] when transposed != 0.  Any A, C, P >= 1
+ * (lines longer than the staged tile go through in chunks).  Returns GF_ERR_UNSUPPORTED (-1) when a size is <= 0. */
+int gf_line_close_counts(const float* end, const uint16_t* dir, const uint16_t* len, const float* pts, const uint8_t* keep,
+                         int32_t* count, int B, int A, int C, int P, float dist_th, int transposed, void* stream);
 
 /* ---- frozen SuperPoint extractor tails (gluefactory/models/extractors/superpoint_open.py; the
  * convolutions stay on the stock library).
