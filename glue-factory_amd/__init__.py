@@ -6,6 +6,7 @@ Imported as ``glue_factory_amd`` (see the shim next to this directory).  Sub-mod
   conf       small OmegaConf-compatible config object
   base_model BaseModel / get_model plugin surface (gluefactory/models/base_model.py)
   matchers   lightglue / superglue / gluestick
+  lines      wireframe extractor (junctions for gluestick) / segments given with the view
   pipeline   TwoViewPipeline-compatible composition
   gt         ground-truth assignment from homographies
   synthetic  seeded synthetic keypoint-pair generator

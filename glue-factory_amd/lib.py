@@ -84,6 +84,10 @@ SIGNATURES = {
     "gf_gt_epi_min": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "gf_gt_depth_reward": [_P] * 10 + [_F, _F, _I, _I, _I, _P],
     "gf_line_close_counts": [_P] * 6 + [_I, _I, _I, _I, _F, _I, _P],
+    "gf_wf_cluster": [_P] * 8 + [_I, _I, _I, _D, _I, _P],
+    "gf_wf_suppress": [_P] * 7 + [_I] * 5 + [_F, _P],
+    "gf_wf_descriptors": [_P] * 5 + [_I] * 8 + [_P],
+    "gf_wf_associativity": [_P, _P, _I, _I, _I, _P],
     "gf_bias_act_bn_nhwc": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "gf_conv1_bias_act_bn": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "gf_conv3x3_c64": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],

@@ -473,6 +473,40 @@ int gf_gt_depth_reward(const float* kp0, const float* kp0_1, const float* kp1, c
 int gf_line_close_counts(const float* end, const uint16_t* dir, const uint16_t* len, const float* pts, const uint8_t* keep,
                          int32_t* count, int B, int A, int C, int P, float dist_th, int transposed, void* stream);
 
+/* ---- wireframe extractor (gluefactory/models/lines/wireframe.py; csrc/wireframe.hip).  Additive: ABI 20 unchanged.
+ * All four write into the CONCATENATED per-image tensors of the extractor's output, P = J + N rows: a junction block of
+ * J = 2 L rows followed by the N keypoints.  Every size argument must be positive (GF_ERR_UNSUPPORTED, -1, before anything is
+ * enqueued; n, J are offsets / counts that may be 0); kernel nodes only, nothing allocated, no host synchronisation.
+ *
+ * gf_wf_cluster (wireframe.py:43-98, the sklearn DBSCAN(eps, min_samples=1) + scatter_reduce_(mean) + fill of
+ *   lines_to_wireframe): one workgroup per image over the n = 2 L end points of lines [B,L,2,2] fp32.  Clusters = connected
+ *   components of the graph with an edge where dx^2 + dy^2 <= eps^2, decided as fp64 arithmetic on the fp32 coordinates
+ *   decides it (inclusive); ids 0..nc-1 in the order of each cluster's lowest end-point index.  Junction position / score =
+ *   fp32 sum of the members (score: line_scores [B,L] repeated twice) in ascending end-point index, divided by the count.
+ *   Writes junc_idx [B,L,2] int64, num_junctions [B] int64, out_lines [B,L,2,2] = junctions[junc_idx], rows 0..nc-1 of
+ *   points [B,P,2] / scores [B,P], and rows nc..2L-1 with fill [B,2L,2] (row for row; NULL = zeros) and score 0.
+ *   merge == 0: every end point is its own junction (the "independent lines" branch, :269-294).  L <= 2048 (coordinates
+ *   and labels resident in LDS), else GF_ERR_UNSUPPORTED; P >= 2 L and eps >= 0, else GF_ERR_SHAPE.
+ * gf_wf_suppress (:186-201): flag [B,N] (one byte) = any end point ends [B,n,2] with fp32 sqrtf(dx*dx + dy*dy) < radius
+ *   (strict, no fused multiply-add: torch's operation order).  Rows J..J+N-1 of points / scores take fill [B,N,2] and 0
+ *   where flagged, kpts [B,N,2] / kscores [B,N] elsewhere.  n == 0 or radius <= 0 flag nothing.
+ * gf_wf_descriptors (:8-19 sample_descriptors_corner_conv, :118, :202-208, :252-254): out [B,P,C] fp32, one wave per row.
+ *   Rows < J and flagged keypoint rows: bilinear sample of map [B,h,w,C] (channels-last, `dtype`) at pixel
+ *   points[b,row] / stride - 0.5 with zero padding, then x / max(|x|_2, 1e-12); the map is NOT normalised per pixel and
+ *   there is no +0.5 (unlike gf_sample_descriptors).  Other keypoint rows: copy of kdesc [B,N,C] fp32 (N = P - J).
+ *   C % 64 == 0 and C <= 512 (GF_ERR_ALIGN).
+ * gf_wf_associativity (:100-104, :256-262): out [B,P,P] one byte per entry (torch.bool) = identity plus both orientations
+ *   of (junc_idx[b,l,0], junc_idx[b,l,1]); the zeros are written by a kernel with 16-byte stores (out 16-byte aligned, else
+ *   GF_ERR_ALIGN; P need not be a multiple of 16).  Index pairs outside [0, P) are ignored. */
+int gf_wf_cluster(const float* lines, const float* line_scores, const float* fill, int64_t* junc_idx,
+                  int64_t* num_junctions, float* out_lines, float* points, float* scores, int B, int L, int P, double eps,
+                  int merge, void* stream);
+int gf_wf_suppress(const float* kpts, const float* kscores, const float* ends, const float* fill, uint8_t* flag,
+                   float* points, float* scores, int B, int N, int n, int P, int J, float radius, void* stream);
+int gf_wf_descriptors(const void* map, const float* points, const float* kdesc, const uint8_t* flag, float* out, int B,
+                      int P, int J, int h, int w, int C, int stride, int dtype, void* stream);
+int gf_wf_associativity(const int64_t* junc_idx, uint8_t* out, int B, int L, int P, void* stream);
+
 /* ---- frozen SuperPoint extractor tails (gluefactory/models/extractors/superpoint_open.py; the
  * convolutions stay on the stock library).
  * gf_bias_act_bn_nhwc: one pass for the VGGBlock tail Conv2d(no bias) -> +bias -> ReLU -> BatchNorm2d(eval)
