@@ -391,6 +391,14 @@ template <typename T> int launch_t(int which, const HeadParams& p, int D, hipStr
     }
 }
 
+// what launch() would answer without enqueuing anything: an entry that touches an output before its launch asks first
+int rejected(const HeadParams& p, int D, int dtype) {
+    if (p.B <= 0 || p.No <= 0 || p.Ns <= 0) return GF_ERR_SHAPE;
+    if (dtype != GF_F32 && dtype != GF_BF16) return GF_ERR_DTYPE;
+    if (D != 64 && D != 128 && D != 256) return GF_ERR_UNSUPPORTED;
+    return 0;
+}
+
 int launch(int which, const HeadParams& p, int D, int dtype, void* stream) {
     if (p.B <= 0 || p.No <= 0 || p.Ns <= 0) return GF_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -435,6 +443,7 @@ extern "C" int gf_assign_write(const void* a, const void* b, const float* rowbia
     p.own = b; p.oth = a; p.B = B; p.No = N; p.Ns = M; p.sbias = rowbias; p.obias = colbias;
     p.alpha = alpha; p.corner = corner; p.g0 = bin_col; p.g1 = bin_row; p.out = out; p.f0 = expsum;
     p.nsplit = GF_WRITE_SPLIT;
+    if (int e = rejected(p, D, dtype)) return e;      // a rejected call leaves expsum as it was
     if (expsum)
         if (hipError_t e = gf_zero_f32(expsum, (size_t)B, reinterpret_cast<hipStream_t>(stream))) return (int)e;
     return launch(K_WRITE, p, D, dtype, stream);

@@ -107,7 +107,8 @@ int gf_attn_bwd_acc(const void* q, const void* k, const void* v, const void* o,
 
 /* ---- assignment head: double softmax with dustbins ------------------------------------------
  * S = a b^T with a [B,M,D], b [B,N,D] (the final_proj outputs, already scaled by D^-1/4),
- * D % 16 == 0, D <= 256, rows contiguous (row stride D, batch strides M*D / N*D).
+ * D in {64, 128, 256} (GF_ERR_UNSUPPORTED otherwise), fp32 or bf16 operands (GF_ERR_DTYPE otherwise), B, M, N > 0
+ * (GF_ERR_SHAPE otherwise), rows contiguous (row stride D, batch strides M*D / N*D).  A rejected call writes nothing.
  *
  * gf_rows_lse: lse[b,i] = log sum_j exp(S_ij + colbias[b,j])   (colbias may be NULL)
  *   Called twice — (a,b) and (b,a) — it gives the row and column normalisers of
@@ -121,7 +122,8 @@ int gf_rows_lse(const void* a, const void* b, const float* colbias, float* lse,
  * With alpha = 2, colbias_j = logsigmoid(z1_j) - c_j this is the row arg-max of the core of the
  * log assignment (lightglue.py:295 `scores[:, :-1, :-1].max(2)`, and the per-layer arg-max of
  * TokenConfidence.loss lightglue.py:81-94) without materialising it; called with (b,a) it
- * gives the column arg-max. */
+ * gives the column arg-max.  The lowest index wins a tie (torch.max's rule); a row whose scores are all -inf (a -inf
+ * colbias on every column) gives rowmax = -inf and rowarg = 0. */
 int gf_rows_argmax(const void* a, const void* b, const float* colbias, float alpha,
                    float* rowmax, int64_t* rowarg,
                    int B, int M, int N, int D, int dtype, void* stream);
@@ -131,7 +133,9 @@ int gf_rows_argmax(const void* a, const void* b, const float* colbias, float alp
  *   lse[b,i]              = log sum_j exp(S_ij)                      (skipped when lse == NULL)
  *   rowmax / rowarg [b,i] = max / argmax_j alpha * S_ij + logsigmoid(bias_z[b,j]) - bias_n[b,j]
  * Three passes give everything a layer's loss needs: c = gf_rows_lse(b, a);
- * (r, max0, arg0) = gf_rows_lse_argmax(a, b, z1, c); (max1, arg1) = gf_rows_lse_argmax(b, a, z0, r, lse=NULL). */
+ * (r, max0, arg0) = gf_rows_lse_argmax(a, b, z1, c); (max1, arg1) = gf_rows_lse_argmax(b, a, z0, r, lse=NULL).
+ * Ties and all -inf rows as in gf_rows_argmax: the lowest index, and rowarg = 0 with rowmax = -inf.  bias_z, bias_n,
+ * rowmax and rowarg must not be NULL (GF_ERR_SHAPE). */
 int gf_rows_lse_argmax(const void* a, const void* b, const float* bias_z, const float* bias_n,
                        float alpha, float* lse, float* rowmax, int64_t* rowarg,
                        int B, int M, int N, int D, int dtype, void* stream);
