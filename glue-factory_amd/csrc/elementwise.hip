@@ -247,7 +247,24 @@ __global__ __launch_bounds__(256) void ln_gelu_fwd_kernel(const T* x, const floa
             if (row + r >= R) break;
             const float md = s[r] * inv_c;
             const float mu = x0[r] + md;
-            const float rs = rsqrtf(fmaxf(q[r] * inv_c - md * md, 0.f) + eps);
+            float var = fmaxf(q[r] * inv_c - md * md, 0.f);
+            // E[d^2] - E[d]^2 loses log2(1 + md^2 / var) bits.  That is harmless while x0 lies within a few sigma of the
+            // mean, but with an outlier in column 0 every d is as large as it: 1.2e-4 of the normalised values at
+            // C = 1024 in fp32, over the 1e-4 parity budget.  Past a loss of 6 bits (x0 more than 7.9 sigma off the
+            // mean) the wave sums (d - md)^2 over its registers instead; md and var are the same in every lane.
+            if (md * md > 63.f * var) {
+                float q2 = 0.f;
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch)
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) {
+                        int col = (ch * 64 + lane) * VEC + e;
+                        float dc = (FULL || col < C) ? (v[r][ch][e] - x0[r]) - md : 0.f;
+                        q2 += dc * dc;
+                    }
+                var = wave_allsum(q2) * inv_c;
+            }
+            const float rs = rsqrtf(var + eps);
 #pragma unroll
             for (int ch = 0; ch < NCH; ++ch)
 #pragma unroll

@@ -656,7 +656,10 @@ int select_kernel(int dtype, int Nout, int K, bool two_source) {
     return dma ? DW_DMA : DW_TR;
 }
 
-hipError_t allow_lds(const void* kernel, int bytes) {            // every tier asks for more than the 48 KiB default
+// Every tier asks for 64 KiB of dynamic LDS or more (64, 80 and 136 KiB).  The limit without this call is not 48 KiB:
+// gf_ln_gelu_bwd at bf16 C = 2048 launches with exactly 65536 bytes and no attribute (tests/test_gpu_elementwise.py,
+// test_ln_gelu[bfloat16-2048]).  Nothing above 64 KiB has been launched without the opt-in, so all three keep it.
+hipError_t allow_lds(const void* kernel, int bytes) {
     return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 

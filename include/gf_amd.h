@@ -575,7 +575,9 @@ int gf_sample_descriptors(const void* map, const float* kpts, float* out, int B,
  * lightglue.py:71,275-276,285-286).  x [M,C] in `dtype`, w [C] fp32, z/dz [M] fp32.
  * gf_rowdot_bwd writes dx = dz * w (+ base, when base != NULL: the running sum of a gradient chain; dx may alias base)
  * when dx != NULL (pass NULL for a detached input) and per-block
- * partials part [gf_rowdot_nblk(M)][C+1] whose column sums are (dw[0..C), db). */
+ * partials part [gf_rowdot_nblk(M)][C+1] whose column sums are (dw[0..C), db).
+ * Accepted C (all four gf_rowdot* entries), VEC = 4 (fp32) / 8 (bf16): C % VEC == 0 and C <= 256 * VEC, otherwise
+ * GF_ERR_UNSUPPORTED; M <= 0 or C <= 0 -> GF_ERR_SHAPE; an unknown dtype -> GF_ERR_DTYPE.  A rejected call writes nothing. */
 int gf_rowdot_nblk(int M);
 int gf_rowdot_fwd(const void* x, const float* w, float bias, const float* bias_dev, float* z, int M, int C, int dtype,
                   void* stream);      /* z = x w + bias + (bias_dev ? *bias_dev : 0): bias_dev = a DEVICE scalar (the nn.Linear bias) */
@@ -635,11 +637,16 @@ int gf_rotary_qk(void* qkv, const float* cs, int B, int N, int H, int D, int inv
  * dtheta [B,N,D/2] (fp32) receives the gradient w.r.t. the pair angles
  * sum_{q,k,heads} (g_odd * y_even - g_even * y_odd), which autograd carries to posenc.Wr;
  * dtheta_base (may be NULL, may alias dtheta): added to it -- the angles are shared by all L layers, so the running sum of
- * the layers whose backward already ran rides in this launch instead of L - 1 separate adds. */
+ * the layers whose backward already ran rides in this launch instead of L - 1 separate adds.
+ * Both entries: B, N, H, D <= 0 or an odd D -> GF_ERR_SHAPE; an unknown dtype -> GF_ERR_DTYPE.  The backward takes
+ * D <= 64 or D == 128 only (the q / k halves of a pair meet inside one wave pass or one lane), any other D ->
+ * GF_ERR_UNSUPPORTED; the forward takes every even D.  The v third is never touched. */
 int gf_rotary_qk_bwd(void* dqkv, const void* qkv_rot, const float* cs, float* dtheta, const float* dtheta_base,
                      int B, int N, int H, int D, int dtype, void* stream);
 /* LayerNorm(affine) + GELU(erf) over rows of x [R, C] (lightglue.py:143-148 ffn.1, ffn.2):
- * y = gelu(ln(x) * gamma + beta); saves mean / rstd [R] for the backward. */
+ * y = gelu(ln(x) * gamma + beta); saves mean / rstd [R] for the backward.
+ * Accepted C (forward and backward), VEC = 4 (fp32) / 8 (bf16): C % VEC == 0 and C <= 256 * VEC, otherwise
+ * GF_ERR_UNSUPPORTED; R <= 0 or C <= 0 -> GF_ERR_SHAPE; an unknown dtype -> GF_ERR_DTYPE. */
 int gf_ln_gelu_fwd(const void* x, const float* gamma, const float* beta, void* y,
                    float* mean, float* rstd, int R, int C, float eps, int dtype, void* stream);
 /* Backward: dx [R,C]; dgamma/dbeta partial sums [nblk, C] fp32 (nblk = gf_ln_gelu_nblk(R)),
