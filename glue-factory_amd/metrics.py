@@ -1,7 +1,10 @@
 """No-grad matcher metrics on the [B,N] match vectors (eval mode only).
 
 Restates gluefactory/models/utils/metrics.py:4-50 (recall, precision, accuracy and the
-ranking average precision of matches0 against gt_matches0); tiny tensors, stock torch ops."""
+ranking average precision of matches0 against gt_matches0); tiny tensors, stock torch ops.
+
+Homography evaluation (gluefactory/geometry/homography.py:314-342, gluefactory/eval/utils.py:137-156, 197-261), batched:
+sym_homography_error, homography_corner_error and homography_metrics, the last on top of the GPU solvers of ``solvers/``."""
 import torch
 
 
@@ -34,3 +37,70 @@ def matcher_metrics(pred, data, prefix="", prefix_gt=None):
         f"{prefix}accuracy": ratio(labelled),
         f"{prefix}average_precision": ap,
     }
+
+
+# ------------------------------------------------------------------------------------------------ homography evaluation
+def _batched(*ts):
+    """Add the batch axis the 3x3 helpers of gt expect where the caller passes one pair."""
+    single = ts[-1].dim() == 2
+    return single, [t[None] if single else t for t in ts]
+
+
+@torch.no_grad()
+def sym_homography_error(kpts0, kpts1, T_0to1):
+    """gluefactory/geometry/homography.py:314-323: mean of the forward and the backward transfer distance.  kpts [B,N,2] and
+    T_0to1 [B,3,3] -> [B,N] (or one pair without the batch axis).  The reference inverts with torch.pinverse; here the
+    adjugate of gt.inv3x3 (the same matrix for an invertible homography, and capturable)."""
+    from .gt import warp_points
+    single, (kpts0, kpts1, T) = _batched(kpts0, kpts1, T_0to1)
+    d01 = ((warp_points(kpts0, T, eps=0.0) - kpts1) ** 2).sum(-1).sqrt()
+    d10 = ((warp_points(kpts1, T, inverse=True, eps=0.0) - kpts0) ** 2).sum(-1).sqrt()
+    err = (d01 + d10) / 2.0
+    return err[0] if single else err
+
+
+@torch.no_grad()
+def homography_corner_error(T, T_gt, image_size):
+    """gluefactory/geometry/homography.py:336-342: mean distance of the four image corners under T and T_gt.  T, T_gt
+    [B,3,3], image_size [B,2] = (W, H) -> [B] (or one pair without the batch axis -> a scalar tensor)."""
+    from .gt import warp_points
+    single, (T, T_gt) = _batched(T, T_gt)
+    size = image_size.to(T).reshape(-1, 2).expand(T.shape[0], 2)
+    W, Hh = size[:, 0], size[:, 1]
+    zero = torch.zeros_like(W)
+    corners = torch.stack([torch.stack([zero, zero], -1), torch.stack([W, zero], -1), torch.stack([W, Hh], -1),
+                           torch.stack([zero, Hh], -1)], -2)
+    d = ((warp_points(corners, T, eps=0.0) - warp_points(corners, T_gt, eps=0.0)) ** 2).sum(-1).sqrt().mean(-1)
+    return d[0] if single else d
+
+
+@torch.no_grad()
+def homography_metrics(pred, data):
+    """Batched restatement of gluefactory/eval/utils.py:137-156 (eval_matches_homography), :241-261 (eval_homography_dlt)
+    and, when ``pred`` carries a solver's output (``M_0to1``, ``inliers``, ``success``), :197-238 (eval_homography_robust).
+    Every value is a [B] tensor.  A pair without matches has precision 0 (the reference's nan_to_num) and infinite errors;
+    a pair whose DLT or RANSAC finds no model has an infinite error."""
+    from .solvers.dlt import homography_dlt
+    kp0, kp1, m0 = pred["keypoints0"], pred["keypoints1"], pred["matches0"]
+    H_gt = data["H_0to1"].float()
+    size = data["view0"]["image_size"].float()
+    valid = m0 > -1
+    nm = valid.sum(1)
+    pts1 = kp1.float().gather(1, m0.clamp(min=0)[..., None].expand(-1, -1, 2))
+    err = sym_homography_error(kp0.float(), pts1, H_gt)
+    inf = torch.full_like(size[:, 0], float("inf"))
+
+    def prec(th):
+        return ((err < th) & valid).float().sum(1) / nm.clamp(min=1)
+
+    out = {"prec@1px": prec(1), "prec@3px": prec(3), "num_matches": nm}
+    H_dlt, ok = homography_dlt(kp0, kp1, m0, pred.get("matching_scores0"))
+    out["H_error_dlt"] = torch.where(ok, homography_corner_error(H_dlt, H_gt, size), inf)
+    if "M_0to1" in pred and "success" in pred:
+        ok_r = pred["success"]
+        out["H_error_ransac"] = torch.where(ok_r, homography_corner_error(pred["M_0to1"].float(), H_gt, size), inf)
+        if "inliers" in pred:
+            ninl = pred["inliers"].float().sum(1)
+            out["ransac_inl"] = ninl
+            out["ransac_inl%"] = ninl / nm.clamp(min=1)
+    return out

@@ -511,6 +511,38 @@ int gf_wf_descriptors(const void* map, const float* points, const float* kdesc, 
                       int P, int J, int h, int w, int C, int stride, int dtype, void* stream);
 int gf_wf_associativity(const int64_t* junc_idx, uint8_t* out, int B, int L, int P, void* stream);
 
+/* ---- homography solver (csrc/h_solver.hip).  Additive: ABI 20 unchanged.
+ * Batched RANSAC + Hartley-normalised DLT on the GPU, standing in for gluefactory/robust_estimators/homography/opencv.py:27-53 (cv2.findHomography(..., cv2.RANSAC, ransac_th): forward transfer
+ * error, identity and all-false inliers when no model is found) and for the find_homography_dlt(pts0, pts1, scores) of
+ * gluefactory/eval/utils.py:241-261.  Kernel nodes only, nothing allocated, no environment read, no host synchronisation;
+ * rejected arguments return an error code before anything is enqueued.
+ * Inputs: kpts0 [B,M,2], kpts1 [B,N,2] fp32, matches0 [B,M] int64 (an index outside [0, N) means no match); correspondence
+ * i is (kpts0[i], kpts1[matches0[i]]).  Pairs may have any number K_b of matches, 0 included; keypoints of unmatched slots
+ * are never read.  ws: gf_h_ws_bytes(B, M, T) bytes of device scratch (T = 1 for gf_h_dlt), 16-byte aligned (GF_ERR_ALIGN);
+ * ws_bytes = the size the caller really holds (GF_ERR_SHAPE when too small).  B, M, N <= 0, T < 1, a NULL required pointer,
+ * ransac_th not in (0, 1e18), lo_iters outside [0, 64]: GF_ERR_SHAPE.
+ * The sampling function, the closed-form 4-point fit, its rejection rules and the inlier rule are stated in the header
+ * comment of csrc/h_solver.hip; tests/h_solver_cases.py restates them on the host.
+ * gf_h_ransac: T hypotheses per pair, all evaluated (no early exit); the winner has the highest integer inlier count, ties
+ *   to the lowest hypothesis index; lo_iters rounds of {DLT refit on the current inliers, rescore, accept when the count does
+ *   not drop}.  4 + 2 lo_iters launches whatever B, K_b and the data.  H [B,3,3] fp32 with H[2][2] == 1 (identity where
+ *   success is 0), inliers [B,M] one byte per keypoint of view 0 (0 for unmatched ones), num_inliers [B] int32, success [B]
+ *   one byte.  samples [B,T,4] int32 (may be NULL): the four indices into the pair's ordered match list (-1 where K_b < 4);
+ *   hyp_counts [B,T] int32 (may be NULL): the inlier count of every hypothesis, -1 for a rejected one.
+ * gf_h_dlt: the refit alone over all matches with the optional weights [B,M] fp32 (NULL = ones; matching_scores0): 3 launches.
+ *   success is 0 (and H the identity) with fewer than 4 matches, with |h22| < GF_H_H22_FRAC ||H||_F or a non-finite entry. */
+#define GF_H_TILE 256        /* correspondences per LDS tile of the scoring kernel */
+#define GF_H_HYPS 256        /* hypotheses per workgroup of the scoring kernel (one per lane) */
+#define GF_H_EPS_AREA 0.5f   /* a sample is rejected when twice the signed area of a point triple is below this (pixels^2) */
+#define GF_H_H22_FRAC 1e-4f  /* a model is rejected when |h22| < GF_H_H22_FRAC ||H||_F */
+#define GF_H_JACOBI 12       /* cyclic Jacobi sweeps of the 9 x 9 eigenproblem */
+int64_t gf_h_ws_bytes(int B, int M, int T);
+int gf_h_ransac(const float* kpts0, const float* kpts1, const int64_t* matches0, int B, int M, int N, int T,
+                float ransac_th, int lo_iters, uint32_t seed, void* ws, int64_t ws_bytes, float* H, uint8_t* inliers,
+                int32_t* num_inliers, uint8_t* success, int32_t* samples, int32_t* hyp_counts, void* stream);
+int gf_h_dlt(const float* kpts0, const float* kpts1, const int64_t* matches0, const float* weights, int B, int M, int N,
+             void* ws, int64_t ws_bytes, float* H, uint8_t* success, void* stream);
+
 /* ---- frozen SuperPoint extractor tails (gluefactory/models/extractors/superpoint_open.py; the
  * convolutions stay on the stock library).
  * gf_bias_act_bn_nhwc: one pass for the VGGBlock tail Conv2d(no bias) -> +bias -> ReLU -> BatchNorm2d(eval)
