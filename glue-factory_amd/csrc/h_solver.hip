@@ -35,6 +35,7 @@
 // de-normalisation, h22 = 1.
 #include "gf_common.h"
 #include "gf_amd.h"
+#include "gf_jacobi9.h"
 
 namespace {
 
@@ -403,37 +404,7 @@ __global__ __launch_bounds__(256) void h_refit_kernel(Ws w, const float* weights
             for (int j = 0; j < 9; ++j) V[i][j] = i == j ? 1. : 0.;
     }
     __syncthreads();
-    // cyclic Jacobi: lane k < 9 owns row k of A (kept symmetric) and of V
-    for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep)
-        for (int p = 0; p < 8; ++p)
-            for (int q = p + 1; q < 9; ++q) {
-                const double app = A[p][p], aqq = A[q][q], apq = A[p][q];
-                double cs = 1., sn = 0., tn = 0.;
-                if (apq != 0.) {
-                    const double theta = (aqq - app) / (2. * apq);
-                    tn = (theta >= 0. ? 1. : -1.) / (fabs(theta) + sqrt(theta * theta + 1.));
-                    cs = 1. / sqrt(tn * tn + 1.);
-                    sn = tn * cs;
-                }
-                double akp = 0., akq = 0., vkp = 0., vkq = 0.;
-                if (tid < 9) { akp = A[tid][p]; akq = A[tid][q]; vkp = V[tid][p]; vkq = V[tid][q]; }
-                __syncthreads();
-                if (tid < 9) {
-                    V[tid][p] = cs * vkp - sn * vkq;
-                    V[tid][q] = sn * vkp + cs * vkq;
-                    if (tid != p && tid != q) {
-                        const double np_ = cs * akp - sn * akq, nq_ = sn * akp + cs * akq;
-                        A[tid][p] = np_; A[p][tid] = np_;
-                        A[tid][q] = nq_; A[q][tid] = nq_;
-                    } else if (tid == p) {
-                        A[p][p] = app - tn * apq;
-                        A[p][q] = 0.; A[q][p] = 0.;
-                    } else {
-                        A[q][q] = aqq + tn * apq;
-                    }
-                }
-                __syncthreads();
-            }
+    gf_jacobi9(A, V, JACOBI_SWEEPS, tid);       // lane k < 9 owns row k of A (kept symmetric) and of V
     if (tid == 0) {
         int best = 0;
         for (int i = 1; i < 9; ++i)

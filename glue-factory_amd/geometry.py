@@ -123,3 +123,39 @@ def sym_epipolar_distance_all(p0, p1, E, eps=1e-15):
     d0 = p1_E_p0 / (E_p0[..., None, 0] ** 2 + E_p0[..., None, 1] ** 2 + eps).sqrt()
     d1 = p1_E_p0 / (Et_p1[..., None, :, 0] ** 2 + Et_p1[..., None, :, 1] ** 2 + eps).sqrt()
     return (d0 + d1) / 2
+
+
+def T_to_E(T):
+    """Essential matrix [t]x R of a pose (gluefactory/geometry/epipolar.py:7-9): x1^T E x0 = 0 in normalised coordinates."""
+    return skew_symmetric(T.t) @ T.R
+
+
+def sym_epipolar_distance(p0, p1, E, squared=True):
+    """Symmetric epipolar distance of N point pairs [..., N] (gluefactory/geometry/epipolar.py:32-56): squared, the sum of
+    the two squared point-to-line distances; else the mean of the two distances.  Points [..., N, 2] or homogeneous."""
+    assert p0.shape[-2] == p1.shape[-2]
+    if p0.shape[-2] == 0:
+        return torch.zeros(p0.shape[:-1]).to(p0)
+
+    def hom(p):
+        return p if p.shape[-1] == 3 else torch.cat([p, p.new_ones(p.shape[:-1] + (1,))], -1)
+    p0, p1 = hom(p0), hom(p1)
+    p1_E_p0 = torch.einsum("...ni,...ij,...nj->...n", p1, E, p0)
+    E_p0 = torch.einsum("...ij,...nj->...ni", E, p0)
+    Et_p1 = torch.einsum("...ij,...ni->...nj", E, p1)
+    d0 = (E_p0[..., 0] ** 2 + E_p0[..., 1] ** 2).clamp(min=1e-6)
+    d1 = (Et_p1[..., 0] ** 2 + Et_p1[..., 1] ** 2).clamp(min=1e-6)
+    if squared:
+        return p1_E_p0 ** 2 * (1 / d0 + 1 / d1)
+    return p1_E_p0.abs() * (1 / d0.sqrt() + 1 / d1.sqrt()) / 2
+
+
+def decompose_essential_matrix(E):
+    """R1 = U W V^T, R2 = U W^T V^T, t = U[:, 2] with det U = det V = +1 (gluefactory/geometry/epipolar.py:97-122), through
+    torch.linalg.svd: the torch statement of what csrc/e_solver.hip computes on the device, for the tests."""
+    U, _, Vt = torch.linalg.svd(E)
+    flip = E.new_tensor([1.0, 1.0, -1.0])
+    U = torch.where((torch.det(U) < 0)[..., None, None], U * flip, U)
+    Vt = torch.where((torch.det(Vt) < 0)[..., None, None], Vt * flip[:, None], Vt)
+    W = E.new_tensor([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+    return U @ W @ Vt, U @ W.transpose(-1, -2) @ Vt, U[..., -1]

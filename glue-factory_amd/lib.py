@@ -91,6 +91,9 @@ SIGNATURES = {
     "gf_h_ws_bytes": [_I, _I, _I],
     "gf_h_ransac": [_P, _P, _P, _I, _I, _I, _I, _F, _I, _c.c_uint32, _P, _L] + [_P] * 7,
     "gf_h_dlt": [_P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P],
+    "gf_e_ws_bytes": [_I, _I, _I],
+    "gf_e_ransac": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _c.c_uint32, _P, _L] + [_P] * 11,
+    "gf_e_pose": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _P],
     "gf_bias_act_bn_nhwc": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "gf_conv1_bias_act_bn": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "gf_conv3x3_c64": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
@@ -116,7 +119,7 @@ SIGNATURES = {
     "gf_ln_gelu_nblk": [_I],
     "gf_ln_gelu_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
 }
-_RESTYPE = {"gf_h_ws_bytes": _c.c_int64, "gf_sinkhorn_ws_bytes": _c.c_int64, "gf_linear_dw_ws_bytes": _c.c_int64}
+_RESTYPE = {"gf_h_ws_bytes": _c.c_int64, "gf_e_ws_bytes": _c.c_int64, "gf_sinkhorn_ws_bytes": _c.c_int64, "gf_linear_dw_ws_bytes": _c.c_int64}
 
 _lib = None
 

@@ -4,7 +4,10 @@ Restates gluefactory/models/utils/metrics.py:4-50 (recall, precision, accuracy a
 ranking average precision of matches0 against gt_matches0); tiny tensors, stock torch ops.
 
 Homography evaluation (gluefactory/geometry/homography.py:314-342, gluefactory/eval/utils.py:137-156, 197-261), batched:
-sym_homography_error, homography_corner_error and homography_metrics, the last on top of the GPU solvers of ``solvers/``."""
+sym_homography_error, homography_corner_error and homography_metrics, the last on top of the GPU solvers of ``solvers/``.
+
+Relative-pose evaluation (gluefactory/geometry/epipolar.py:127-155, gluefactory/utils/tools.py:137-149,
+gluefactory/eval/utils.py:41-70, 159-194), batched: relative_pose_error, pose_auc and relative_pose_metrics."""
 import torch
 
 
@@ -99,6 +102,69 @@ def homography_metrics(pred, data):
     if "M_0to1" in pred and "success" in pred:
         ok_r = pred["success"]
         out["H_error_ransac"] = torch.where(ok_r, homography_corner_error(pred["M_0to1"].float(), H_gt, size), inf)
+        if "inliers" in pred:
+            ninl = pred["inliers"].float().sum(1)
+            out["ransac_inl"] = ninl
+            out["ransac_inl%"] = ninl / nm.clamp(min=1)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- relative-pose evaluation
+@torch.no_grad()
+def relative_pose_error(T_gt, R, t, ignore_gt_t_thr=0.0, eps=1e-10):
+    """gluefactory/geometry/epipolar.py:127-155, batched on the device: (t_err, r_err) in degrees, each [B] (or scalars for
+    one pair).  T_gt: a Pose (or anything with .R [B,3,3] and .t [B,3]).  The translation angle folds at 90 degrees (the
+    sign of t is not observable from E); where |t_gt| < ignore_gt_t_thr it is 0, as in the reference."""
+    R_gt, t_gt = T_gt.R.to(R), T_gt.t.to(t)
+    n = (t.norm(dim=-1) * t_gt.norm(dim=-1)).clamp(min=eps)
+    t_err = torch.rad2deg(torch.arccos(((t * t_gt).sum(-1) / n).clamp(-1.0, 1.0)))
+    t_err = torch.minimum(t_err, 180 - t_err)
+    t_err = torch.where(t_gt.norm(dim=-1) < ignore_gt_t_thr, torch.zeros_like(t_err), t_err)
+    cos = ((R.transpose(-1, -2) @ R_gt).diagonal(dim1=-2, dim2=-1).sum(-1) - 1) / 2
+    r_err = torch.rad2deg(torch.arccos(cos.clamp(-1.0, 1.0)).abs())
+    return t_err, r_err
+
+
+def pose_auc(errors, thresholds):
+    """cal_error_auc of gluefactory/utils/tools.py:137-149, rounding to 4 places included: the area under the recall curve
+    of ``errors`` (a tensor or a sequence; inf = failure) up to every threshold, divided by the threshold."""
+    import numpy as np
+    if torch.is_tensor(errors):
+        errors = errors.detach().double().cpu().numpy()
+    e = np.sort(np.asarray(errors, np.float64).reshape(-1))
+    recall = np.r_[0.0, (np.arange(len(e)) + 1) / len(e)]
+    e = np.r_[0.0, e]
+    aucs = []
+    for th in thresholds:
+        last = np.searchsorted(e, th)
+        r = np.r_[recall[:last], recall[last - 1]]
+        x = np.r_[e[:last], th]
+        aucs.append(float(np.round(np.sum((x[1:] - x[:-1]) * (r[1:] + r[:-1]) / 2) / th, 4)))
+    return aucs
+
+
+@torch.no_grad()
+def relative_pose_metrics(pred, data):
+    """Batched restatement of gluefactory/eval/utils.py:41-70 (eval_matches_epipolar) and, when ``pred`` carries a solver's
+    output (``M_0to1``, ``inliers``, ``success``), :159-194 (eval_relative_pose_robust).  Every value is a [B] tensor.  A pair
+    without matches has precision 0 (the reference's nan_to_num); a pair without a model has an infinite pose error."""
+    from .geometry import T_to_E, sym_epipolar_distance
+    kp0, kp1, m0 = pred["keypoints0"], pred["keypoints1"], pred["matches0"]
+    cam0, cam1, T_gt = data["view0"]["camera"], data["view1"]["camera"], data["T_0to1"]
+    valid = m0 > -1
+    nm = valid.sum(1)
+    pts1 = kp1.float().gather(1, m0.clamp(min=0)[..., None].expand(-1, -1, 2))
+    p0 = cam0.image2cam(kp0.float())
+    err = sym_epipolar_distance(p0, cam1.image2cam(pts1).to(p0.dtype), T_to_E(T_gt).to(p0.dtype), squared=False)
+
+    def prec(th):
+        return ((err < th) & valid).float().sum(1) / nm.clamp(min=1)
+
+    out = {"epi_prec@1e-4": prec(1e-4), "epi_prec@5e-4": prec(5e-4), "epi_prec@1e-3": prec(1e-3), "num_matches": nm}
+    if "M_0to1" in pred and "success" in pred:
+        M = pred["M_0to1"]
+        t_err, r_err = relative_pose_error(T_gt, M.R.float(), M.t.float())
+        out["rel_pose_error"] = torch.where(pred["success"], torch.maximum(t_err, r_err), torch.full_like(t_err, float("inf")))
         if "inliers" in pred:
             ninl = pred["inliers"].float().sum(1)
             out["ransac_inl"] = ninl

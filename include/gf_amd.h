@@ -543,6 +543,46 @@ int gf_h_ransac(const float* kpts0, const float* kpts1, const int64_t* matches0,
 int gf_h_dlt(const float* kpts0, const float* kpts1, const int64_t* matches0, const float* weights, int B, int M, int N,
              void* ws, int64_t ws_bytes, float* H, uint8_t* success, void* stream);
 
+/* ---- relative-pose solver (csrc/e_solver.hip, csrc/e_fivept.h).  Additive: ABI 20 unchanged.
+ * Batched 5-point RANSAC, eight-point refit and pose recovery on the GPU, standing in for
+ * gluefactory/robust_estimators/relative_pose/opencv.py:23-64 (cv2.findEssentialMat on normalised coordinates with the
+ * threshold ransac_th / f_mean, then cv2.recoverPose) and decompose_essential_matrix of gluefactory/geometry/epipolar.py:97-122.
+ * Kernel nodes only, nothing allocated, no environment read, no host synchronisation; rejected arguments return an error code
+ * before anything is enqueued.
+ * Inputs: pts0n [B,M,2], pts1n [B,N,2] fp32 NORMALISED image coordinates (camera.image2cam(kpts)[..., :2]), matches0 [B,M]
+ * int64 (an index outside [0, N) means no match), th [B] fp32 the inlier threshold of every pair in normalised units (a pair
+ * whose th is zero or NaN has no inliers).  Pairs may have any number K_b of matches, 0 included.  ws: gf_e_ws_bytes(B, M, T)
+ * bytes of device scratch (T = 1 for gf_e_pose), 16-byte aligned (GF_ERR_ALIGN); ws_bytes = the size the caller really holds
+ * (GF_ERR_SHAPE when too small).  B, M, N <= 0, T < 1, a NULL required pointer, lo_iters outside [0, 64]: GF_ERR_SHAPE.
+ * The sampling function, the minimal solver, the inlier rule, the refit and the depth test are stated in the header comments
+ * of csrc/e_solver.hip and csrc/e_fivept.h; tests/e_solver_cases.py restates them on the host.
+ * gf_e_ransac: T hypotheses per pair, up to GF_E_MAXSOL candidates each, all evaluated (no early exit); the winner has the
+ *   highest integer inlier count, ties to the lowest (hypothesis, candidate) index; lo_iters rounds of {refit on the current
+ *   inliers, rescore, accept when the count does not drop}, the refit skipped under 8 inliers.  5 + 2 lo_iters launches
+ *   whatever B, K_b and the data.  E [B,3,3] fp32 with ||E||_F = 1 (x1^T E x0 = 0), R [B,3,3], t [B,3] with |t| = 1,
+ *   inliers [B,M] one byte per keypoint of view 0, num_inliers [B] int32, success [B] one byte: 1 when K_b >= 5 and some
+ *   sample gave a candidate (whatever its inlier count); else E = 0, R = I, t = 0, no inliers.  Debug outputs (each may be
+ *   NULL): samples [B,T,5] int32 (-1 where K_b < 5), cand [B,T,GF_E_MAXSOL,9] fp32 (unused slots zero), ncand [B,T] int32,
+ *   cand_counts [B,T,GF_E_MAXSOL] int32 (-1 for an unused slot).
+ * gf_e_pose: the pose stage alone: of the four decompositions of E [B,3,3] the one with the most correspondences flagged in
+ *   inliers [B,M] (bytes, per keypoint of view 0) at positive depth in both cameras, ties to the lowest index in the order
+ *   (R1, t), (R1, -t), (R2, t), (R2, -t); num_front [B] int32 its count.  2 launches.  A non-finite or rank-0 E: R = I, t = 0. */
+#define GF_E_TILE 256          /* correspondences per LDS tile of the scoring kernel */
+#define GF_E_HYPS 256          /* candidates per workgroup of the scoring kernel (one per lane) */
+#define GF_E_MAXSOL 10         /* candidates per hypothesis: the real roots of the degree-10 polynomial (cv2's 5-point solver returns up to 10 too) */
+#define GF_E_EPS_PIVOT 1e-12   /* a sample is rejected when a pivot of its two eliminations is below this (rows of unit scale); stands in for cv2's degenerate-sample check */
+#define GF_E_BISECT 32         /* bisections per bracket of the root finder: [-1, 1] down to 5e-10, the Gauss-Newton steps do the rest */
+#define GF_E_POLISH 3          /* Gauss-Newton steps on the ten cubic equations after the back-substitution */
+#define GF_E_JACOBI 12         /* cyclic Jacobi sweeps of the 9 x 9 eigenproblem of the refit (as GF_H_JACOBI) */
+#define GF_E_JACOBI3 8         /* cyclic Jacobi sweeps of the 3 x 3 eigenproblem of E^T E (torch.svd in epipolar.py:99) */
+int64_t gf_e_ws_bytes(int B, int M, int T);
+int gf_e_ransac(const float* pts0n, const float* pts1n, const int64_t* matches0, const float* th, int B, int M, int N, int T,
+                int lo_iters, uint32_t seed, void* ws, int64_t ws_bytes, float* E, float* R, float* t, uint8_t* inliers,
+                int32_t* num_inliers, uint8_t* success, int32_t* samples, float* cand, int32_t* ncand, int32_t* cand_counts,
+                void* stream);
+int gf_e_pose(const float* pts0n, const float* pts1n, const int64_t* matches0, const uint8_t* inliers, const float* E, int B,
+              int M, int N, void* ws, int64_t ws_bytes, float* R, float* t, int32_t* num_front, void* stream);
+
 /* ---- frozen SuperPoint extractor tails (gluefactory/models/extractors/superpoint_open.py; the
  * convolutions stay on the stock library).
  * gf_bias_act_bn_nhwc: one pass for the VGGBlock tail Conv2d(no bias) -> +bias -> ReLU -> BatchNorm2d(eval)
