@@ -9,12 +9,11 @@
 // lo_iters x (refit, rescore), pose; 2 for gf_e_pose: compact, pose).  Nothing depends on a count the host reads: every
 // kernel takes its pair's match count K_b from the workspace.
 //
-// Sampling (restated on the host by tests/e_solver_cases.py, bit for bit).  All arithmetic is uint32 with wrap-around:
-//   hash(seed, pair, hyp, draw): x = seed * 0x9E3779B1 + pair * 0x85EBCA77 + hyp * 0xC2B2AE3D + draw * 0x27D4EB2F + 0x165667B1;
-//                                x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16
-//   (the hash of h_solver.hip).  Draw d = 0..4 of a pair with K matches: r = (uint64(hash) * (K - d)) >> 32, uniform in
-//   [0, K - d); then the skip mapping: the earlier draws are visited in ASCENDING order of their value p, and r += 1 whenever
-//   r >= p.  The five values are distinct indices into the pair's ordered match list.
+// The RANSAC machinery (workspace core, sampling, reductions and the winner key, compaction, the tile-streamed count, flag
+// pass, rescore, the skeleton of the refit, flag scatter) is ransac_common.h, shared with h_solver.hip; what is here is the
+// model: the 5-point solve, the Sampson rule, the rows and the view-1 side of the eight-point fit, the pose.
+//
+// Sampling: five draws per hypothesis by the rule in the header of ransac_common.h.
 //
 // Solve: one hypothesis per lane, 64 lanes per workgroup, fp64, the arithmetic of e_fivept.h (Nister's solver: null space by
 // elimination, the 10 x 20 cubic constraints, elimination to a degree-10 polynomial, bisection on fixed brackets, back-
@@ -25,21 +24,17 @@
 // Score: one candidate per lane, candidate index = hypothesis * GF_E_MAXSOL + slot.  Correspondence (x0, x1) is an inlier of
 // E when, in fp32 with e = x1^T E x0, a = (E x0)[0:2], b = (E^T x1)[0:2]:  e^2 < th^2 (|a|^2 + |b|^2)  and the right-hand
 // side is finite and > 0 (the squared Sampson error against th^2 without a division).  The compacted correspondences stream
-// through LDS in tiles of GF_E_TILE, read as broadcasts.  A workgroup's best (count, lowest candidate index) is one 64-bit
-// key, the select kernel takes the maximum key: deterministic, no floating-point atomics.
+// through LDS in tiles of GF_E_TILE.
 //
-// Refit (skipped under 8 inliers): fp64.  Hartley normalisation of both point sets over the flagged correspondences, the 45
-// distinct sums of A^T A (rows (u x, u y, u, v x, v y, v, x, y, 1)) through a fixed-order block reduction, GF_E_JACOBI cyclic
-// sweeps (gf_jacobi9.h), the eigenvector of the smallest eigenvalue, de-normalisation E = T1^T G T0, projection to singular
+// Refit (skipped under 8 inliers): the skeleton of ransac_common.h over the flagged correspondences with the rows
+// (u x, u y, u, v x, v y, v, x, y, 1) of A^T A and GF_E_JACOBI sweeps, then E = T1^T G T0 and the projection to singular
 // values (1, 1, 0) / sqrt 2 through GF_E_JACOBI3 sweeps on E^T E.
 //
 // Pose: one workgroup per pair, fp64.  R1 = U W V^T, R2 = U W^T V^T, t = U[:, 2] with det U = det V = +1; the four
 // candidates in the order (R1, t), (R1, -t), (R2, t), (R2, -t).  Every flagged correspondence is triangulated linearly
 // (X = d0 x0 from the least squares of x1 x (d0 R x0 + t) = 0) and counts for a candidate when d0 > 0 and (R X + t)_z > 0;
 // fixed-order integer reduction; the highest count wins, ties to the lowest index.  |t| = 1.
-#include "gf_common.h"
-#include "gf_amd.h"
-#include "gf_jacobi9.h"
+#include "ransac_common.h"
 #include "e_fivept.h"
 
 namespace {
@@ -49,142 +44,39 @@ constexpr int HYPS = GF_E_HYPS;
 constexpr int MAXSOL = GF_E_MAXSOL;
 constexpr int SOLVE_LANES = 64;
 static_assert(HYPS == 256, "one candidate per lane of a 256-lane workgroup");
-static_assert(TILE == 256, "one correspondence per lane when a tile is staged");
 
-struct Ws {
-    int* K;                     // [B] matches of the pair
-    int* idx;                   // [B, M] ordered indices of the matched keypoints of view 0
-    float4* corr;               // [B, M] (x0, y0, x1, y1) of the ordered matches
+struct Ws : RansacWs {          // the models (cur, refit) are essential matrices with ||E||_F = 1
     float* cand;                // [B, T, MAXSOL, 9] candidates of every hypothesis
     int* ncand;                 // [B, T]
-    unsigned long long* best;   // [B, nblk] best key of every scoring workgroup
-    float* Ecur;                // [B, 12] current model (9 used)
-    float* Enew;                // [B, 12] refitted model
-    int* state;                 // [B, 4] {count of the current model, current model valid, refit valid, unused}
-    uint8_t* flags;             // [B, M] inlier flags of the current model over the ordered matches
 };
 
-inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 inline int64_t nblk_of(int T) { return ((int64_t)T * MAXSOL + HYPS - 1) / HYPS; }
 
 inline size_t carve(void* base, int B, int M, int T, Ws* w) {
-    size_t off = 0;
-    char* p = reinterpret_cast<char*>(base);
-    auto take = [&](size_t bytes) { size_t o = off; off = al16(off + bytes); return p + o; };
+    Carver c{reinterpret_cast<char*>(base)};
     Ws t;
-    t.K = reinterpret_cast<int*>(take(sizeof(int) * (size_t)B));
-    t.idx = reinterpret_cast<int*>(take(sizeof(int) * (size_t)B * M));
-    t.corr = reinterpret_cast<float4*>(take(sizeof(float4) * (size_t)B * M));
-    t.cand = reinterpret_cast<float*>(take(sizeof(float) * 9 * MAXSOL * (size_t)B * T));
-    t.ncand = reinterpret_cast<int*>(take(sizeof(int) * (size_t)B * T));
-    t.best = reinterpret_cast<unsigned long long*>(take(sizeof(unsigned long long) * (size_t)B * nblk_of(T)));
-    t.Ecur = reinterpret_cast<float*>(take(sizeof(float) * 12 * (size_t)B));
-    t.Enew = reinterpret_cast<float*>(take(sizeof(float) * 12 * (size_t)B));
-    t.state = reinterpret_cast<int*>(take(sizeof(int) * 4 * (size_t)B));
-    t.flags = reinterpret_cast<uint8_t*>(take((size_t)B * M));
+    carve_core(c, B, M, nblk_of(T), t);
+    t.cand = c.take<float>(9 * MAXSOL * (size_t)B * T);
+    t.ncand = c.take<int>((size_t)B * T);
     if (w) *w = t;
-    return off;
+    return c.off;
 }
 
-// ---- sampling ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t e_hash(uint32_t seed, uint32_t pair, uint32_t hyp, uint32_t draw) {
-    uint32_t x = seed * 0x9E3779B1u + pair * 0x85EBCA77u + hyp * 0xC2B2AE3Du + draw * 0x27D4EB2Fu + 0x165667B1u;
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    return x;
-}
-
-// five distinct indices in [0, K), K >= 5
-__device__ __forceinline__ void sample5(uint32_t seed, int pair, int hyp, int K, int s[5]) {
-    int o[5];                                      // the earlier draws in ascending order
-#pragma unroll
-    for (int d = 0; d < 5; ++d) {
-        int r = (int)(((unsigned long long)e_hash(seed, (uint32_t)pair, (uint32_t)hyp, (uint32_t)d) * (uint32_t)(K - d)) >> 32);
-#pragma unroll
-        for (int q = 0; q < d; ++q)
-            if (r >= o[q]) ++r;
-        s[d] = r;
-        int at = d;
-#pragma unroll
-        for (int q = d - 1; q >= 0; --q)
-            if (o[q] > r) { o[q + 1] = o[q]; at = q; }
-        o[at] = r;
+struct Inlier {
+    __device__ __forceinline__ bool operator()(const float* E, float4 c, float th2) const {
+        const float a0 = E[0] * c.x + E[1] * c.y + E[2], a1 = E[3] * c.x + E[4] * c.y + E[5], a2 = E[6] * c.x + E[7] * c.y + E[8];
+        const float e = c.z * a0 + c.w * a1 + a2;
+        const float b0 = E[0] * c.z + E[3] * c.w + E[6], b1 = E[1] * c.z + E[4] * c.w + E[7];
+        const float rhs = th2 * (a0 * a0 + a1 * a1 + b0 * b0 + b1 * b1);
+        return (e * e < rhs) && (rhs > 0.f) && isfinite(rhs);           // a NaN compares false
     }
-}
-
-__device__ __forceinline__ bool is_inlier(const float E[9], float4 c, float th2) {
-    const float a0 = E[0] * c.x + E[1] * c.y + E[2], a1 = E[3] * c.x + E[4] * c.y + E[5], a2 = E[6] * c.x + E[7] * c.y + E[8];
-    const float e = c.z * a0 + c.w * a1 + a2;
-    const float b0 = E[0] * c.z + E[3] * c.w + E[6], b1 = E[1] * c.z + E[4] * c.w + E[7];
-    const float rhs = th2 * (a0 * a0 + a1 * a1 + b0 * b0 + b1 * b1);
-    return (e * e < rhs) && (rhs > 0.f) && isfinite(rhs);           // a NaN compares false
-}
-
-// ---- block reductions (256 lanes = 4 waves), results in every lane ---------------------------------------------------------
-__device__ __forceinline__ int block_sum_int(int v, int* red) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    __syncthreads();                              // red may still be read from an earlier call
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
-template <int NV> __device__ __forceinline__ void block_sum_f64(double (&v)[NV], double* red /* [4][NV] */) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v[i] += __shfl_xor(v[i], d);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) red[(threadIdx.x >> 6) * NV + i] = v[i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = ((red[i] + red[NV + i]) + red[2 * NV + i]) + red[3 * NV + i];
-}
-
-__device__ __forceinline__ unsigned long long block_max_key(unsigned long long key, unsigned long long* red) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(key, d);
-        key = o > key ? o : key;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
-    __syncthreads();
-    unsigned long long m = red[0];
-    for (int q = 1; q < 4; ++q) m = red[q] > m ? red[q] : m;
-    return m;
-}
+};
 
 // ---- kernels ----------------------------------------------------------------------------------------------------------
-// ordered compaction of the matches of one pair (ascending i); a match index outside [0, N) counts as no match
 __global__ __launch_bounds__(256) void e_compact_kernel(const float* kp0, const float* kp1, const int64_t* m0, Ws w, int M,
                                                         int N) {
     __shared__ int wsum[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int base = 0;
-    for (int i0 = 0; i0 < M; i0 += 256) {
-        const int i = i0 + tid;
-        const int64_t j = i < M ? m0[(int64_t)b * M + i] : -1;
-        const bool f = j >= 0 && j < N;
-        const unsigned long long mask = __ballot(f);
-        const int pre = __popcll(mask & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wv] = __popcll(mask);
-        __syncthreads();
-        int off = base;
-        for (int q = 0; q < wv; ++q) off += wsum[q];
-        const int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (f) {
-            const int64_t at = (int64_t)b * M + off + pre;
-            const float* p = kp0 + ((int64_t)b * M + i) * 2;
-            const float* q = kp1 + ((int64_t)b * N + j) * 2;
-            w.idx[at] = i;
-            w.corr[at] = make_float4(p[0], p[1], q[0], q[1]);
-        }
-        base += tot;
-        __syncthreads();
-    }
-    if (tid == 0) w.K[b] = base;
+    compact_pair(kp0, kp1, m0, w, blockIdx.x, M, N, wsum);
 }
 
 // one 5-point hypothesis per lane -> its candidates in the workspace (and in the debug outputs)
@@ -198,7 +90,7 @@ __global__ __launch_bounds__(SOLVE_LANES) void e_solve_kernel(Ws w, int M, int T
     int s[5] = {-1, -1, -1, -1, -1};
     int n = 0;
     if (K >= 5) {
-        sample5(seed, b, t, K, s);
+        sample_distinct<5>(seed, b, t, K, s);
         double pts[20];
 #pragma unroll
         for (int d = 0; d < 5; ++d) {
@@ -230,63 +122,30 @@ __global__ __launch_bounds__(256) void e_score_kernel(Ws w, const float* th, int
     if (ci < T * MAXSOL) ok = (ci % MAXSOL) < w.ncand[(int64_t)b * T + ci / MAXSOL];
 #pragma unroll
     for (int i = 0; i < 9; ++i) E[i] = ok ? w.cand[((int64_t)b * T * MAXSOL + ci) * 9 + i] : 0.f;   // zero: no inlier
-    int count = 0;
-    for (int k0 = 0; k0 < K; k0 += TILE) {
-        const int n = min(TILE, K - k0);
-        __syncthreads();
-        if (tid < n) tile[tid] = corr[k0 + tid];
-        __syncthreads();
-        for (int k = 0; k < n; ++k) count += is_inlier(E, tile[k], th2) ? 1 : 0;
-    }
+    const int count = tile_count<TILE>(E, corr, K, th2, tile, Inlier());
     if (cand_counts != nullptr && ci < T * MAXSOL) cand_counts[(int64_t)b * T * MAXSOL + ci] = ok ? count : -1;
-    // key: (count + 1) in the high word (0 = no candidate), ~index in the low word: the maximum key is the highest count at
-    // the lowest index
-    const unsigned long long key =
-        ok ? (((unsigned long long)(uint32_t)(count + 1) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)ci)) : 0ull;
-    const unsigned long long m = block_max_key(key, red);
+    const unsigned long long m = block_max_key(pack_key(ok, count, ci), red);
     if (tid == 0) w.best[(int64_t)b * nblk + blk] = m;
 }
 
-// flags and count of model E over the ordered matches of pair b; the count is returned in every lane
-__device__ __forceinline__ int flag_pass(const float* E, const float4* corr, uint8_t* flags, int K, float th2, int* red) {
-    int count = 0;
-    for (int k = threadIdx.x; k < K; k += 256) {
-        const bool in = is_inlier(E, corr[k], th2);
-        if (flags != nullptr) flags[k] = in ? 1 : 0;
-        count += in ? 1 : 0;
-    }
-    return block_sum_int(count, red);
-}
-
-// winner of the pair's workgroups -> current model, its flags and its count
+// winner of the pair's workgroups, read back from the candidates -> current model, its flags and its count
 __global__ __launch_bounds__(256) void e_select_kernel(Ws w, const float* th, int M, int T, int nblk) {
     __shared__ unsigned long long red[4];
     __shared__ int ired[4];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x;
     const int K = w.K[b];
     const float thb = th[b], th2 = thb * thb;
-    const float4* corr = w.corr + (int64_t)b * M;
-    unsigned long long key = 0ull;
-    for (int q = tid; q < nblk; q += 256) {
-        const unsigned long long o = w.best[(int64_t)b * nblk + q];
-        key = o > key ? o : key;
-    }
-    const unsigned long long m = block_max_key(key, red);
+    const unsigned long long m = pair_max_key(w, b, nblk, red);
     const bool ok = m != 0ull && K >= 5;
     float E[9];
-    const int64_t ci = ok ? (int64_t)(0xFFFFFFFFu - (uint32_t)(m & 0xFFFFFFFFull)) : 0;
+    const int64_t ci = ok ? (int64_t)key_index(m) : 0;
 #pragma unroll
     for (int i = 0; i < 9; ++i) E[i] = ok ? w.cand[((int64_t)b * T * MAXSOL + ci) * 9 + i] : 0.f;   // zero flags nothing
-    const int count = flag_pass(E, corr, w.flags + (int64_t)b * M, K, th2, ired);
-    if (tid < 9) w.Ecur[(int64_t)b * 12 + tid] = E[tid];
-    if (tid == 0) {
-        w.state[b * 4 + 0] = count;
-        w.state[b * 4 + 1] = ok ? 1 : 0;
-        w.state[b * 4 + 2] = 0;
-    }
+    set_current(w, b, M, K, E, E, ok, th2, ired, Inlier());
 }
 
-// Hartley-normalised eight-point fit over the flagged matches, projected onto the essential manifold -> Enew, state[2]
+// Hartley-normalised eight-point fit over the flagged matches, projected onto the essential manifold -> refit,
+// state[ST_REFIT_OK]
 __global__ __launch_bounds__(256) void e_refit_kernel(Ws w, int M) {
     __shared__ double red[4 * 45];
     __shared__ double A[9][9], V[9][9];
@@ -294,100 +153,43 @@ __global__ __launch_bounds__(256) void e_refit_kernel(Ws w, int M) {
     const int K = w.K[b];
     const float4* corr = w.corr + (int64_t)b * M;
     const uint8_t* flags = w.flags + (int64_t)b * M;
-    float* En = w.Enew + (int64_t)b * 12;
-    if (w.state[b * 4 + 1] == 0 || w.state[b * 4 + 0] < 8) {        // uniform over the workgroup
-        if (tid == 0) w.state[b * 4 + 2] = 0;
+    float* En = w.refit + (int64_t)b * 12;
+    if (w.state[b * 4 + ST_CUR_OK] == 0 || w.state[b * 4 + ST_COUNT] < 8) {        // uniform over the workgroup
+        if (tid == 0) w.state[b * 4 + ST_REFIT_OK] = 0;
         return;
     }
-    // pass 1: count and centroids
-    double s5[5] = {0., 0., 0., 0., 0.};
-    for (int k = tid; k < K; k += 256)
-        if (flags[k]) {
-            const float4 c = corr[k];
-            s5[0] += 1.; s5[1] += c.x; s5[2] += c.y; s5[3] += c.z; s5[4] += c.w;
-        }
-    block_sum_f64<5>(s5, red);
-    const double n = s5[0];
-    const double cx0 = s5[1] / n, cy0 = s5[2] / n, cx1 = s5[3] / n, cy1 = s5[4] / n;
-    // pass 2: mean distances to the centroids
-    double s2[2] = {0., 0.};
-    for (int k = tid; k < K; k += 256)
-        if (flags[k]) {
-            const float4 c = corr[k];
-            const double dx0 = c.x - cx0, dy0 = c.y - cy0, dx1 = c.z - cx1, dy1 = c.w - cy1;
-            s2[0] += sqrt(dx0 * dx0 + dy0 * dy0);
-            s2[1] += sqrt(dx1 * dx1 + dy1 * dy1);
-        }
-    block_sum_f64<2>(s2, red);
-    const double sc0 = 1.4142135623730951 / (s2[0] / n), sc1 = 1.4142135623730951 / (s2[1] / n);
-    // pass 3: the 45 distinct sums of A^T A
-    double acc[45];
-#pragma unroll
-    for (int i = 0; i < 45; ++i) acc[i] = 0.;
-    for (int k = tid; k < K; k += 256)
-        if (flags[k]) {
-            const float4 c = corr[k];
-            const double x = (c.x - cx0) * sc0, y = (c.y - cy0) * sc0, u = (c.z - cx1) * sc1, v = (c.w - cy1) * sc1;
-            const double r[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.};
-            int at = 0;
-#pragma unroll
-            for (int i = 0; i < 9; ++i)
-#pragma unroll
-                for (int j = i; j < 9; ++j) { acc[at] += r[i] * r[j]; ++at; }
-        }
-    block_sum_f64<45>(acc, red);
-    __syncthreads();
-    if (tid == 0) {
+    auto keep = [&](int k) { return flags[k] != 0; };
+    Hartley t;
+    refit_centroids(corr, K, red, t, keep);
+    double m[9];
+    refit_solve(corr, K, red, A, V, GF_E_JACOBI, t, m, keep, [&](double (&acc)[45], int, double x, double y, double u, double v) {
+        const double r[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.};
         int at = 0;
+#pragma unroll
         for (int i = 0; i < 9; ++i)
-            for (int j = i; j < 9; ++j) { A[i][j] = acc[at]; A[j][i] = acc[at]; ++at; }
-        for (int i = 0; i < 9; ++i)
-            for (int j = 0; j < 9; ++j) V[i][j] = i == j ? 1. : 0.;
-    }
-    __syncthreads();
-    gf_jacobi9(A, V, GF_E_JACOBI, tid);
+#pragma unroll
+            for (int j = i; j < 9; ++j) { acc[at] += r[i] * r[j]; ++at; }
+    });
     if (tid == 0) {
-        int best = 0;
-        for (int i = 1; i < 9; ++i)
-            if (A[i][i] < A[best][best]) best = i;
-        double g[9], m[9], e[9];
-        for (int i = 0; i < 9; ++i) g[i] = V[i][best];
-        // E = T1^T G T0 with T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]]
-        for (int r = 0; r < 3; ++r) {
-            m[3 * r + 0] = g[3 * r + 0] * sc0;
-            m[3 * r + 1] = g[3 * r + 1] * sc0;
-            m[3 * r + 2] = g[3 * r + 2] - sc0 * (g[3 * r + 0] * cx0 + g[3 * r + 1] * cy0);
-        }
+        // E = T1^T (G T0) with T1 = [[s1, 0, -s1 cx1], [0, s1, -s1 cy1], [0, 0, 1]]
+        double e[9];
         for (int c = 0; c < 3; ++c) {
-            e[0 + c] = sc1 * m[0 + c];
-            e[3 + c] = sc1 * m[3 + c];
-            e[6 + c] = m[6 + c] - sc1 * (cx1 * m[0 + c] + cy1 * m[3 + c]);
+            e[0 + c] = t.sc1 * m[0 + c];
+            e[3 + c] = t.sc1 * m[3 + c];
+            e[6 + c] = m[6 + c] - t.sc1 * (t.cx1 * m[0 + c] + t.cy1 * m[3 + c]);
         }
         bool ok = gf_e5::project_essential(e);
         float out[9];
         for (int i = 0; i < 9; ++i) { out[i] = (float)e[i]; ok = ok && isfinite(out[i]); }
         for (int i = 0; i < 9; ++i) En[i] = ok ? out[i] : 0.f;
-        w.state[b * 4 + 2] = ok ? 1 : 0;
+        w.state[b * 4 + ST_REFIT_OK] = ok ? 1 : 0;
     }
 }
 
-// rescore the refit; it replaces the current model when it is valid and its count does not drop
 __global__ __launch_bounds__(256) void e_rescore_kernel(Ws w, const float* th, int M) {
     __shared__ int ired[4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    if (w.state[b * 4 + 1] == 0 || w.state[b * 4 + 2] == 0) return;           // uniform
-    const int K = w.K[b];
-    const float thb = th[b], th2 = thb * thb;
-    const float4* corr = w.corr + (int64_t)b * M;
-    float E[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) E[i] = w.Enew[(int64_t)b * 12 + i];
-    const int count = flag_pass(E, corr, nullptr, K, th2, ired);
-    if (count < w.state[b * 4 + 0]) return;                                   // uniform
-    flag_pass(E, corr, w.flags + (int64_t)b * M, K, th2, ired);
-    __syncthreads();
-    if (tid < 9) w.Ecur[(int64_t)b * 12 + tid] = E[tid];
-    if (tid == 0) w.state[b * 4 + 0] = count;
+    const int b = blockIdx.x;
+    rescore_pair(w, b, M, [=]() { const float thb = th[b]; return thb * thb; }, ired, Inlier());
 }
 
 // pose of the model by the depth test, and the outputs.  ransac != 0: the current model and its flags from the workspace,
@@ -401,8 +203,8 @@ __global__ __launch_bounds__(256) void e_pose_kernel(Ws w, int M, int ransac, co
     const int K = w.K[b];
     const float4* corr = w.corr + (int64_t)b * M;
     const int* idx = w.idx + (int64_t)b * M;
-    const float* Esrc = ransac ? w.Ecur + (int64_t)b * 12 : E_in + (int64_t)b * 9;
-    const bool model = ransac ? w.state[b * 4 + 1] != 0 : true;
+    const float* Esrc = ransac ? w.cur + (int64_t)b * 12 : E_in + (int64_t)b * 9;
+    const bool model = ransac ? w.state[b * 4 + ST_CUR_OK] != 0 : true;
     if (tid == 0) {
         double E[9];
         bool ok = model;
@@ -446,23 +248,14 @@ __global__ __launch_bounds__(256) void e_pose_kernel(Ws w, int M, int ransac, co
     if (!ransac) return;
     if (tid == 0) {
         success[b] = ok ? 1 : 0;
-        num_inliers[b] = ok ? w.state[b * 4 + 0] : 0;
+        num_inliers[b] = ok ? w.state[b * 4 + ST_COUNT] : 0;
     }
-    for (int i = tid; i < M; i += 256) inliers[(int64_t)b * M + i] = 0;
-    __syncthreads();
-    if (!ok) return;
-    for (int k = tid; k < K; k += 256)
-        if (w.flags[(int64_t)b * M + k]) inliers[(int64_t)b * M + idx[k]] = 1;
+    scatter_flags(w, b, M, ok, inliers);
 }
 
 inline int check_common(const void* p0, const void* p1, const void* m0, int B, int M, int N, int T, const void* ws,
                         int64_t ws_bytes) {
-    if (B <= 0 || M <= 0 || N <= 0 || T < 1) return GF_ERR_SHAPE;
-    if (p0 == nullptr || p1 == nullptr || m0 == nullptr || ws == nullptr) return GF_ERR_SHAPE;
-    if ((int64_t)B * nblk_of(T) >= ((int64_t)1 << 31) || (int64_t)B * T * MAXSOL >= ((int64_t)1 << 31)) return GF_ERR_UNSUPPORTED;
-    if (ws_bytes < (int64_t)carve(nullptr, B, M, T, nullptr)) return GF_ERR_SHAPE;
-    if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) return GF_ERR_ALIGN;
-    return 0;
+    return ransac_check(p0, p1, m0, B, M, N, T, ws, ws_bytes, nblk_of(T), (int64_t)T * MAXSOL, carve(nullptr, B, M, T, nullptr));
 }
 
 }  // namespace

@@ -1,0 +1,339 @@
+// RANSAC skeleton shared by the two-view solvers (h_solver.hip, e_solver.hip): the workspace core, the counter-based
+// sampling, the fixed-order block reductions and the winner key, ordered compaction, the tile-streamed inlier count, the flag
+// pass and the rescore, the Hartley-normalised 9 x 9 refit and the flag scatter.  A solver supplies its inlier rule and the
+// rows of its design matrix as functors and keeps its own __global__ kernels: one workgroup of 256 lanes per pair, except
+// where its header says otherwise.  Nothing depends on a count the host reads: every piece takes the pair's match count K_b
+// from the workspace.
+//
+// Sampling (restated on the host by tests/ransac_cases.py, bit for bit).  All arithmetic is uint32 with wrap-around:
+//   hash(seed, pair, hyp, draw): x = seed * 0x9E3779B1 + pair * 0x85EBCA77 + hyp * 0xC2B2AE3D + draw * 0x27D4EB2F + 0x165667B1;
+//                                x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16
+//   draw d = 0..S-1 of a pair with K matches: r = (uint64(hash) * (K - d)) >> 32, i.e. uniform in [0, K - d); then the skip
+//   mapping: the earlier draws are visited in ASCENDING order of their value p, and r += 1 whenever r >= p.  The S values are
+//   distinct indices into the pair's ordered match list.
+//
+// Winner: a scoring lane packs (count + 1) into the high word of a 64-bit key (0 = no model) and ~index into the low word, so
+// the maximum key is the highest count at the lowest index: deterministic, no floating-point atomics.
+//
+// Refit: fp64 throughout.  Hartley normalisation over the kept correspondences (centroid, mean distance sqrt 2), the 45
+// distinct sums of the normal matrix through a fixed-order block reduction, cyclic Jacobi sweeps on the 9 x 9 matrix in LDS
+// (gf_jacobi9.h), the eigenvector of the smallest eigenvalue, de-normalisation on the view-0 side.
+#pragma once
+#include "gf_common.h"
+#include "gf_amd.h"
+#include "gf_jacobi9.h"
+
+namespace {
+
+// ---- workspace --------------------------------------------------------------------------------------------------------
+struct RansacWs {
+    int* K;                     // [B] matches of the pair
+    int* idx;                   // [B, M] ordered indices of the matched keypoints of view 0
+    float4* corr;               // [B, M] (x0, y0, x1, y1) of the ordered matches
+    unsigned long long* best;   // [B, nblk] best key of every scoring workgroup
+    float* cur;                 // [B, 12] current model (9 used)
+    float* refit;               // [B, 12] refitted model
+    int* state;                 // [B, 4] the words below, one unused
+    uint8_t* flags;             // [B, M] inlier flags of the current model over the ordered matches
+};
+// words of state[b * 4 + .]
+constexpr int ST_COUNT = 0;      // inlier count of the current model
+constexpr int ST_CUR_OK = 1;     // the pair has a current model
+constexpr int ST_REFIT_OK = 2;   // the last refit gave a valid model
+
+// hands out consecutive 16-byte aligned arrays of a buffer (a null buffer: only the size is wanted)
+struct Carver {
+    char* p;
+    size_t off = 0;
+    template <typename T> T* take(size_t count) {
+        const size_t o = off;
+        off = (off + sizeof(T) * count + 15) & ~(size_t)15;
+        return reinterpret_cast<T*>(p + o);
+    }
+};
+
+inline void carve_core(Carver& c, int B, int M, int64_t nblk, RansacWs& w) {
+    w.K = c.take<int>((size_t)B);
+    w.idx = c.take<int>((size_t)B * M);
+    w.corr = c.take<float4>((size_t)B * M);
+    w.best = c.take<unsigned long long>((size_t)B * nblk);
+    w.cur = c.take<float>(12 * (size_t)B);
+    w.refit = c.take<float>(12 * (size_t)B);
+    w.state = c.take<int>(4 * (size_t)B);
+    w.flags = c.take<uint8_t>((size_t)B * M);
+}
+
+// argument checks common to the entry points: nblk scoring workgroups and `lanes` scoring lanes per pair, `need` workspace bytes
+inline int ransac_check(const void* p0, const void* p1, const void* m0, int B, int M, int N, int T, const void* ws,
+                        int64_t ws_bytes, int64_t nblk, int64_t lanes, size_t need) {
+    if (B <= 0 || M <= 0 || N <= 0 || T < 1) return GF_ERR_SHAPE;
+    if (p0 == nullptr || p1 == nullptr || m0 == nullptr || ws == nullptr) return GF_ERR_SHAPE;
+    if ((int64_t)B * nblk >= ((int64_t)1 << 31) || (int64_t)B * lanes >= ((int64_t)1 << 31)) return GF_ERR_UNSUPPORTED;
+    if (ws_bytes < (int64_t)need) return GF_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) return GF_ERR_ALIGN;
+    return 0;
+}
+
+// ---- sampling ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t hash32(uint32_t seed, uint32_t pair, uint32_t hyp, uint32_t draw) {
+    uint32_t x = seed * 0x9E3779B1u + pair * 0x85EBCA77u + hyp * 0xC2B2AE3Du + draw * 0x27D4EB2Fu + 0x165667B1u;
+    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+    return x;
+}
+
+// S distinct indices in [0, K), K >= S
+template <int S> __device__ __forceinline__ void sample_distinct(uint32_t seed, int pair, int hyp, int K, int s[S]) {
+    int o[S];                                      // the earlier draws in ascending order
+#pragma unroll
+    for (int d = 0; d < S; ++d) {
+        int r = (int)(((unsigned long long)hash32(seed, (uint32_t)pair, (uint32_t)hyp, (uint32_t)d) * (uint32_t)(K - d)) >> 32);
+#pragma unroll
+        for (int q = 0; q < d; ++q)
+            if (r >= o[q]) ++r;
+        s[d] = r;
+        int at = d;
+#pragma unroll
+        for (int q = d - 1; q >= 0; --q)
+            if (o[q] > r) { o[q + 1] = o[q]; at = q; }
+        o[at] = r;
+    }
+}
+
+// ---- block reductions (256 lanes = 4 waves), results in every lane ---------------------------------------------------------
+__device__ __forceinline__ int block_sum_int(int v, int* red) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    __syncthreads();                              // red may still be read from an earlier call
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+template <int NV> __device__ __forceinline__ void block_sum_f64(double (&v)[NV], double* red /* [4][NV] */) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v[i] += __shfl_xor(v[i], d);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int i = 0; i < NV; ++i) red[(threadIdx.x >> 6) * NV + i] = v[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = ((red[i] + red[NV + i]) + red[2 * NV + i]) + red[3 * NV + i];
+}
+
+__device__ __forceinline__ unsigned long long block_max_key(unsigned long long key, unsigned long long* red) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(key, d);
+        key = o > key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
+    __syncthreads();
+    unsigned long long m = red[0];
+    for (int q = 1; q < 4; ++q) m = red[q] > m ? red[q] : m;
+    return m;
+}
+
+// ---- winner key -----------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long pack_key(bool ok, int count, int index) {
+    return ok ? (((unsigned long long)(uint32_t)(count + 1) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)index)) : 0ull;
+}
+__device__ __forceinline__ int key_index(unsigned long long key) {
+    return (int)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull));
+}
+
+// maximum key of the pair's scoring workgroups
+__device__ __forceinline__ unsigned long long pair_max_key(const RansacWs& w, int b, int nblk, unsigned long long* red) {
+    unsigned long long key = 0ull;
+    for (int q = threadIdx.x; q < nblk; q += 256) {
+        const unsigned long long o = w.best[(int64_t)b * nblk + q];
+        key = o > key ? o : key;
+    }
+    return block_max_key(key, red);
+}
+
+// ---- compaction -----------------------------------------------------------------------------------------------------------
+// ordered compaction of the matches of pair b (ascending i); a match index outside [0, N) counts as no match
+__device__ __forceinline__ void compact_pair(const float* kp0, const float* kp1, const int64_t* m0, const RansacWs& w, int b,
+                                             int M, int N, int* wsum /* [4] */) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int base = 0;
+    for (int i0 = 0; i0 < M; i0 += 256) {
+        const int i = i0 + tid;
+        const int64_t j = i < M ? m0[(int64_t)b * M + i] : -1;
+        const bool f = j >= 0 && j < N;
+        const unsigned long long mask = __ballot(f);
+        const int pre = __popcll(mask & ((1ull << lane) - 1ull));
+        if (lane == 0) wsum[wv] = __popcll(mask);
+        __syncthreads();
+        int off = base;
+        for (int q = 0; q < wv; ++q) off += wsum[q];
+        const int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (f) {
+            const int64_t at = (int64_t)b * M + off + pre;
+            const float* p = kp0 + ((int64_t)b * M + i) * 2;
+            const float* q = kp1 + ((int64_t)b * N + j) * 2;
+            w.idx[at] = i;
+            w.corr[at] = make_float4(p[0], p[1], q[0], q[1]);
+        }
+        base += tot;
+        __syncthreads();
+    }
+    if (tid == 0) w.K[b] = base;
+}
+
+// ---- scoring, flags, rescore ------------------------------------------------------------------------------------------------
+// inlier count of this lane's model: the pair's correspondences stream through LDS in tiles, every lane reads the same
+// address (a broadcast).  inlier(model, correspondence, th2) is the solver's rule.
+template <int TILE, typename Inlier>
+__device__ __forceinline__ int tile_count(const float* model, const float4* corr, int K, float th2, float4* tile, Inlier inlier) {
+    int count = 0;
+    for (int k0 = 0; k0 < K; k0 += TILE) {
+        const int n = min(TILE, K - k0);
+        __syncthreads();
+        for (int k = threadIdx.x; k < n; k += 256) tile[k] = corr[k0 + k];
+        __syncthreads();
+        for (int k = 0; k < n; ++k) count += inlier(model, tile[k], th2) ? 1 : 0;
+    }
+    return count;
+}
+
+// flags (where wanted) and count of a model over the ordered matches of one pair; the count is returned in every lane
+template <typename Inlier>
+__device__ __forceinline__ int flag_pass(const float* model, const float4* corr, uint8_t* flags, int K, float th2, int* red,
+                                         Inlier inlier) {
+    int count = 0;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const bool in = inlier(model, corr[k], th2);
+        if (flags != nullptr) flags[k] = in ? 1 : 0;
+        count += in ? 1 : 0;
+    }
+    return block_sum_int(count, red);
+}
+
+// the select kernels end here: the flags and the count of `model` (all zero where !ok: it flags nothing) and `kept`, what
+// the workspace holds as the current model, become the state of pair b
+template <typename Inlier>
+__device__ __forceinline__ void set_current(const RansacWs& w, int b, int M, int K, const float* model, const float* kept,
+                                            bool ok, float th2, int* red, Inlier inlier) {
+    const int tid = threadIdx.x;
+    const int count = flag_pass(model, w.corr + (int64_t)b * M, w.flags + (int64_t)b * M, K, th2, red, inlier);
+    if (tid < 9) w.cur[(int64_t)b * 12 + tid] = kept[tid];
+    if (tid == 0) {
+        w.state[b * 4 + ST_COUNT] = count;
+        w.state[b * 4 + ST_CUR_OK] = ok ? 1 : 0;
+        w.state[b * 4 + ST_REFIT_OK] = 0;
+    }
+}
+
+// rescore the refit; it replaces the current model when it is valid and its count does not drop.  threshold() gives th^2 of
+// the pair (asked for only where there is something to rescore)
+template <typename Threshold, typename Inlier>
+__device__ __forceinline__ void rescore_pair(const RansacWs& w, int b, int M, Threshold threshold, int* red, Inlier inlier) {
+    const int tid = threadIdx.x;
+    if (w.state[b * 4 + ST_CUR_OK] == 0 || w.state[b * 4 + ST_REFIT_OK] == 0) return;       // uniform
+    const int K = w.K[b];
+    const float th2 = threshold();
+    const float4* corr = w.corr + (int64_t)b * M;
+    float model[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) model[i] = w.refit[(int64_t)b * 12 + i];
+    const int count = flag_pass(model, corr, nullptr, K, th2, red, inlier);
+    if (count < w.state[b * 4 + ST_COUNT]) return;                                          // uniform
+    flag_pass(model, corr, w.flags + (int64_t)b * M, K, th2, red, inlier);
+    __syncthreads();
+    if (tid < 9) w.cur[(int64_t)b * 12 + tid] = model[tid];
+    if (tid == 0) w.state[b * 4 + ST_COUNT] = count;
+}
+
+// inliers[b, :] = the flags of the current model scattered to the keypoints of view 0 (all zero where !ok)
+__device__ __forceinline__ void scatter_flags(const RansacWs& w, int b, int M, bool ok, uint8_t* inliers) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < M; i += 256) inliers[(int64_t)b * M + i] = 0;
+    __syncthreads();
+    if (!ok) return;
+    const int K = w.K[b];
+    for (int k = tid; k < K; k += 256)
+        if (w.flags[(int64_t)b * M + k]) inliers[(int64_t)b * M + w.idx[(int64_t)b * M + k]] = 1;
+}
+
+// ---- refit ------------------------------------------------------------------------------------------------------------------
+// Hartley normalisation of the kept correspondences: x' = (x - c) sc in either view
+struct Hartley {
+    double n, cx0, cy0, cx1, cy1, sc0, sc1;
+};
+
+// pass 1: count and centroids of the correspondences k < K with keep(k), in every lane.  The caller gates on n before
+// refit_solve (n == 0 leaves the centroids undefined).
+template <typename Keep>
+__device__ __forceinline__ void refit_centroids(const float4* corr, int K, double* red, Hartley& t, Keep keep) {
+    double s5[5] = {0., 0., 0., 0., 0.};
+    for (int k = threadIdx.x; k < K; k += 256)
+        if (keep(k)) {
+            const float4 c = corr[k];
+            s5[0] += 1.; s5[1] += c.x; s5[2] += c.y; s5[3] += c.z; s5[4] += c.w;
+        }
+    block_sum_f64<5>(s5, red);
+    t.n = s5[0];
+    t.cx0 = s5[1] / t.n; t.cy0 = s5[2] / t.n; t.cx1 = s5[3] / t.n; t.cy1 = s5[4] / t.n;
+}
+
+// passes 2 and 3 and the eigenvector: the scales of t; rows(acc, k, x, y, u, v) adds correspondence k's share of the 45
+// distinct sums (i <= j, row-major) of the 9 x 9 normal matrix from its normalised coordinates; the eigenvector g of the
+// smallest eigenvalue; m = G T0 with T0 = [[s0, 0, -s0 cx0], [0, s0, -s0 cy0], [0, 0, 1]], in lane 0 alone.  red is [4][45],
+// lane k < 9 owns row k of A and of V.
+template <typename Keep, typename Rows>
+__device__ __forceinline__ void refit_solve(const float4* corr, int K, double* red, double (*A)[9], double (*V)[9], int sweeps,
+                                            Hartley& t, double m[9], Keep keep, Rows rows) {
+    const int tid = threadIdx.x;
+    const double cx0 = t.cx0, cy0 = t.cy0, cx1 = t.cx1, cy1 = t.cy1;
+    // pass 2: mean distances to the centroids
+    double s2[2] = {0., 0.};
+    for (int k = tid; k < K; k += 256)
+        if (keep(k)) {
+            const float4 c = corr[k];
+            const double dx0 = c.x - cx0, dy0 = c.y - cy0, dx1 = c.z - cx1, dy1 = c.w - cy1;
+            s2[0] += sqrt(dx0 * dx0 + dy0 * dy0);
+            s2[1] += sqrt(dx1 * dx1 + dy1 * dy1);
+        }
+    block_sum_f64<2>(s2, red);
+    const double sc0 = 1.4142135623730951 / (s2[0] / t.n), sc1 = 1.4142135623730951 / (s2[1] / t.n);
+    t.sc0 = sc0; t.sc1 = sc1;
+    // pass 3: the 45 distinct sums
+    double acc[45];
+#pragma unroll
+    for (int i = 0; i < 45; ++i) acc[i] = 0.;
+    for (int k = tid; k < K; k += 256)
+        if (keep(k)) {
+            const float4 c = corr[k];
+            const double x = (c.x - cx0) * sc0, y = (c.y - cy0) * sc0, u = (c.z - cx1) * sc1, v = (c.w - cy1) * sc1;
+            rows(acc, k, x, y, u, v);
+        }
+    block_sum_f64<45>(acc, red);
+    __syncthreads();
+    if (tid == 0) {
+        int at = 0;
+        for (int i = 0; i < 9; ++i)
+            for (int j = i; j < 9; ++j) { A[i][j] = acc[at]; A[j][i] = acc[at]; ++at; }
+        for (int i = 0; i < 9; ++i)
+            for (int j = 0; j < 9; ++j) V[i][j] = i == j ? 1. : 0.;
+    }
+    __syncthreads();
+    gf_jacobi9(A, V, sweeps, tid);
+    if (tid == 0) {
+        int best = 0;
+        for (int i = 1; i < 9; ++i)
+            if (A[i][i] < A[best][best]) best = i;
+        double g[9];
+        for (int i = 0; i < 9; ++i) g[i] = V[i][best];
+        for (int r = 0; r < 3; ++r) {
+            m[3 * r + 0] = g[3 * r + 0] * sc0;
+            m[3 * r + 1] = g[3 * r + 1] * sc0;
+            m[3 * r + 2] = g[3 * r + 2] - sc0 * (g[3 * r + 0] * cx0 + g[3 * r + 1] * cy0);
+        }
+    }
+}
+
+}  // namespace

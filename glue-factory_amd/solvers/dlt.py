@@ -16,8 +16,9 @@ def _prep(kpts0, kpts1, matches0):
     return kpts0.float().contiguous(), kpts1.float().contiguous(), matches0.long().contiguous(), b, m, n
 
 
-def workspace(b, m, t, device):
-    nbytes = int(_lib.load().gf_h_ws_bytes(b, m, t))
+def workspace(entry, b, m, t, device):
+    """The workspace of a solver call: entry = "gf_h_ws_bytes" or "gf_e_ws_bytes"."""
+    nbytes = int(getattr(_lib.load(), entry)(b, m, t))
     return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
 
 
@@ -38,7 +39,7 @@ def homography_dlt(kpts0, kpts1, matches0, weights=None):
         if weights is not None:
             assert weights.shape == (b, m)
             wt = weights.float().contiguous()
-        ws, nbytes = workspace(b, m, 1, dev)
+        ws, nbytes = workspace("gf_h_ws_bytes", b, m, 1, dev)
         _lib.check(_lib.load().gf_h_dlt(kp0.data_ptr(), kp1.data_ptr(), m0.data_ptr(), None if wt is None else wt.data_ptr(),
                                         b, m, n, ws.data_ptr(), nbytes, H.data_ptr(), success.data_ptr(),
                                         torch.cuda.current_stream().cuda_stream), "gf_h_dlt")

@@ -34,7 +34,7 @@ def homography_ransac(kpts0, kpts1, matches0, ransac_th=3.0, max_iters=3000, lo_
             return out
         samples = torch.empty((b, t, 4), dtype=torch.int32, device=dev) if debug else None
         counts = torch.empty((b, t), dtype=torch.int32, device=dev) if debug else None
-        ws, nbytes = workspace(b, m, t, dev)
+        ws, nbytes = workspace("gf_h_ws_bytes", b, m, t, dev)
         _lib.check(_lib.load().gf_h_ransac(
             kp0.data_ptr(), kp1.data_ptr(), m0.data_ptr(), b, m, n, t, float(ransac_th), int(lo_iters), int(seed) & 0xFFFFFFFF,
             ws.data_ptr(), nbytes, H.data_ptr(), inl.data_ptr(), num.data_ptr(), success.data_ptr(),

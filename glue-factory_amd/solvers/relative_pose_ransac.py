@@ -15,12 +15,7 @@ from .. import lib as _lib
 from ..base_model import BaseModel
 from ..conf import Conf
 from ..geometry import Pose
-from .dlt import _prep
-
-
-def _workspace(b, m, t, device):
-    nbytes = int(_lib.load().gf_e_ws_bytes(b, m, t))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+from .dlt import _prep, workspace
 
 
 def _normalised(kpts, camera):
@@ -64,7 +59,7 @@ def relative_pose_ransac(kpts0, kpts1, matches0, camera0, camera1, ransac_th=0.5
                    "cand": torch.empty((b, t, 10, 3, 3), dtype=torch.float32, device=dev),
                    "ncand": torch.empty((b, t), dtype=torch.int32, device=dev),
                    "cand_counts": torch.empty((b, t, 10), dtype=torch.int32, device=dev)}
-        ws, nbytes = _workspace(b, m, t, dev)
+        ws, nbytes = workspace("gf_e_ws_bytes", b, m, t, dev)
         _lib.check(_lib.load().gf_e_ransac(
             p0.data_ptr(), p1.data_ptr(), m0.data_ptr(), th.data_ptr(), b, m, n, t, int(lo_iters), int(seed) & 0xFFFFFFFF,
             ws.data_ptr(), nbytes, E.data_ptr(), R.data_ptr(), tv.data_ptr(), inl.data_ptr(), num.data_ptr(),
@@ -89,7 +84,7 @@ def recover_pose(pts0n, pts1n, matches0, inliers, E):
         R = torch.empty((b, 3, 3), dtype=torch.float32, device=dev)
         t = torch.empty((b, 3), dtype=torch.float32, device=dev)
         nf = torch.empty((b,), dtype=torch.int32, device=dev)
-        ws, nbytes = _workspace(b, m, 1, dev)
+        ws, nbytes = workspace("gf_e_ws_bytes", b, m, 1, dev)
         _lib.check(_lib.load().gf_e_pose(p0.data_ptr(), p1.data_ptr(), m0.data_ptr(), flags.data_ptr(), Ec.data_ptr(), b, m, n,
                                          ws.data_ptr(), nbytes, R.data_ptr(), t.data_ptr(), nf.data_ptr(),
                                          torch.cuda.current_stream().cuda_stream), "gf_e_pose")

@@ -2,8 +2,9 @@
 derived bounds and the mutations the bounds must catch.  No GPU, no torch.  tests/test_e_solver_cases_reference.py tests
 this module itself; tests/test_gpu_e_solver.py compares the kernels with it.
 
-Restated here from the header comments of the two files: the 5-draw counter-based sampling (bit for bit), the Sampson rule,
-the refit and the decomposition with the depth test.  The 5-point solver goes ANOTHER ROUTE than the kernel's: null space by
+Restated here from the header comments of the two files: the Sampson rule, the refit and the decomposition with the depth
+test; the 5-draw counter-based sampling (bit for bit) and the compaction are restated from the header comment of
+csrc/ransac_common.h in tests/ransac_cases.py.  The 5-point solver goes ANOTHER ROUTE than the kernel's: null space by
 numpy.linalg.svd (the kernel: elimination), the ten cubic constraints in graded order reduced by numpy.linalg.solve, the
 10 x 10 action matrix of multiplication by x and numpy.linalg.eig (the kernel: a hidden variable, a degree-10 polynomial in
 z and bisection).  The depth test goes another route too: homogeneous DLT triangulation through a 4 x 4 SVD."""
@@ -12,6 +13,8 @@ import os
 import re
 
 import numpy as np
+
+import ransac_cases as rc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -52,41 +55,11 @@ COND_MAX = 1e7
 NOISY_MARGIN_DEG = 0.1
 
 
-# ---- sampling ----------------------------------------------------------------------------------------------------------
-def hash32(seed, pair, hyp, draw):
-    m = 0xFFFFFFFF
-    x = (seed * 0x9E3779B1 + pair * 0x85EBCA77 + hyp * 0xC2B2AE3D + draw * 0x27D4EB2F + 0x165667B1) & m
-    x ^= x >> 16
-    x = (x * 0x7FEB352D) & m
-    x ^= x >> 15
-    x = (x * 0x846CA68B) & m
-    x ^= x >> 16
-    return x
-
-
-def sample5(seed, pair, hyp, K):
-    out = []
-    for d in range(5):
-        r = (hash32(seed, pair, hyp, d) * (K - d)) >> 32
-        for p in sorted(out):
-            if r >= p:
-                r += 1
-        out.append(r)
-    return out
-
-
-def samples(seed, pair, T, K):
-    """[T,5] int32; -1 everywhere when K < 5 (what the kernel writes)."""
-    if K < 5:
-        return np.full((T, 5), -1, np.int32)
-    return np.array([sample5(seed, pair, t, K) for t in range(T)], np.int32)
-
-
-def compact(kpts0, kpts1, matches0):
-    """Ordered compaction: (idx [K], corr [K,4]) with corr = (x0, y0, x1, y1)."""
-    n = kpts1.shape[0]
-    idx = np.nonzero((matches0 >= 0) & (matches0 < n))[0]
-    return idx, np.concatenate([kpts0[idx], kpts1[matches0[idx]]], -1)
+# ---- sampling and compaction: the shared skeleton with five draws (samples: [T,5] int32, -1 everywhere when K < 5) --------
+hash32 = rc.hash32
+sample5 = functools.partial(rc.sample_distinct, 5)
+samples = functools.partial(rc.samples, 5)
+compact = rc.compact
 
 
 # ---- 5-point solver, fp64, by the action matrix ----------------------------------------------------------------------------

@@ -2,8 +2,9 @@
 mutations the bounds must catch.  No GPU, no torch.  tests/test_h_solver_cases_reference.py tests this module itself;
 tests/test_gpu_h_solver.py compares the kernels with it.
 
-Restated here, from the header comment of csrc/h_solver.hip: the counter-based sampling function (bit for bit), the
-degeneracy tests, the closed-form 4-point fit and the forward transfer error.  The weighted DLT is restated through
+Restated here, from the header comment of csrc/h_solver.hip: the degeneracy tests, the closed-form 4-point fit and the
+forward transfer error; the counter-based sampling (bit for bit) and the compaction are restated from the header comment of
+csrc/ransac_common.h in tests/ransac_cases.py.  The weighted DLT is restated through
 numpy.linalg.svd: kornia is not available here, so `dlt` restates the PUBLISHED meaning of its find_homography_dlt
 (normalise both point sets to zero mean and mean distance sqrt 2 without the weights, stack the two rows per point, weight
 the rows, take the right singular vector of the smallest singular value, de-normalise, divide by h22)."""
@@ -12,6 +13,8 @@ import os
 import re
 
 import numpy as np
+
+import ransac_cases as rc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -29,36 +32,11 @@ U32 = 2.0 ** -24              # unit roundoff of fp32
 SIZE = (640.0, 480.0)         # frame of the corner error
 
 
-# ---- sampling ----------------------------------------------------------------------------------------------------------
-def hash32(seed, pair, hyp, draw):
-    m = 0xFFFFFFFF
-    x = (seed * 0x9E3779B1 + pair * 0x85EBCA77 + hyp * 0xC2B2AE3D + draw * 0x27D4EB2F + 0x165667B1) & m
-    x ^= x >> 16
-    x = (x * 0x7FEB352D) & m
-    x ^= x >> 15
-    x = (x * 0x846CA68B) & m
-    x ^= x >> 16
-    return x
-
-
-def sample4(seed, pair, hyp, K, off_by_one=False):
-    """The four indices of hypothesis `hyp` of pair `pair` with K >= 4 matches.  off_by_one: the mutated skip mapping
-    (`>` for `>=`), which can return an index twice."""
-    out = []
-    for d in range(4):
-        r = (hash32(seed, pair, hyp, d) * (K - d)) >> 32
-        for p in sorted(out):
-            if (r > p) if off_by_one else (r >= p):
-                r += 1
-        out.append(r)
-    return out
-
-
-def samples(seed, pair, T, K, **kw):
-    """[T,4] int32; -1 everywhere when K < 4 (what the kernel writes)."""
-    if K < 4:
-        return np.full((T, 4), -1, np.int32)
-    return np.array([sample4(seed, pair, t, K, **kw) for t in range(T)], np.int32)
+# ---- sampling and compaction: the shared skeleton with four draws (samples: [T,4] int32, -1 everywhere when K < 4) --------
+hash32 = rc.hash32
+sample4 = functools.partial(rc.sample_distinct, 4)
+samples = functools.partial(rc.samples, 4)
+compact = functools.partial(rc.compact, dtype=np.float64)
 
 
 # ---- 4-point fit, vectorised over hypotheses -------------------------------------------------------------------------------
@@ -261,13 +239,6 @@ def corner_bound(p0, p1, w=None, size=SIZE):
 
 
 # ---- host RANSAC (fp64): what the kernels are compared with --------------------------------------------------------------
-def compact(kpts0, kpts1, matches0):
-    """Ordered matched indices of view 0 and their correspondences [K,4] (an index outside [0, N) is no match)."""
-    idx = np.nonzero((matches0 >= 0) & (matches0 < kpts1.shape[0]))[0]
-    corr = np.concatenate([kpts0[idx], kpts1[matches0[idx]]], -1).astype(np.float64).reshape(-1, 4)
-    return idx, corr
-
-
 def host_ransac(kpts0, kpts1, matches0, pair, T, lo_iters=2, seed=SEED, th=TH, backward=False, off_by_one=False):
     """The solver in fp64.  Returns dict(H, inliers [M] bool, num, success, samples [T,4], fit (see fit4), counts [T],
     models: the winning and every refitted model (for the band check of the scenes))."""

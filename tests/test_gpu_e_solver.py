@@ -5,7 +5,7 @@ GF_E_MAXSOL of the header).  Every raw call is made twice into guarded buffers a
 alone.
 
 Two identical pairs at DIFFERENT batch positions cannot give equal bits of E: the pair index is an argument of the sampling
-hash (as in h_solver.hip), so they draw different samples.  What is asserted instead: the same pair at the same position
+hash (ransac_common.h, for either solver), so they draw different samples.  What is asserted instead: the same pair at the same position
 gives equal bits whatever else is in the batch and in a second call, and identical pairs at different positions give the
 same inlier mask and count on a planted scene."""
 import functools
@@ -15,65 +15,28 @@ import pytest
 import torch
 
 import e_solver_cases as ec
+import solver_harness as sh
+from solver_harness import dev as _dev, load as _lib
 
 pytestmark = pytest.mark.gpu
 
-G = 64                         # guard elements on either side of every output and of the workspace
-OUT = ("E", "R", "t", "inliers", "num", "success", "samples", "cand", "ncand", "counts")
-
-
-def _lib():
-    from glue_factory_amd import lib
-    return lib, lib.load()
-
-
-def _guarded(shape, dtype, fill):
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * G,), fill, dtype=dtype, device="cuda")
-    return buf, buf[G:G + n].view(shape)
-
-
-def _intact(buf, fill, what):
-    assert bool((buf[:G] == fill).all()) and bool((buf[-G:] == fill).all()), f"guard band of {what} overwritten"
-
-
-def _dev(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda().contiguous()
-
 
 def _ransac_once(p0, p1, m0, th, T, lo_iters, seed):
-    lib, L = _lib()
     B, M = m0.shape
     N = p1.shape[1]
-    nbytes = int(L.gf_e_ws_bytes(B, M, T))
-    assert nbytes > 0 and nbytes % 16 == 0
-    ws_buf, ws = _guarded((nbytes,), torch.uint8, 0x5A)
     S = ec.MAXSOL
     spec = {"E": ((B, 3, 3), torch.float32, -7.0), "R": ((B, 3, 3), torch.float32, -7.0), "t": ((B, 3), torch.float32, -7.0),
             "inliers": ((B, M), torch.uint8, 0xAB), "num": ((B,), torch.int32, -77), "success": ((B,), torch.uint8, 0xAB),
             "samples": ((B, T, 5), torch.int32, -77), "cand": ((B, T, S, 3, 3), torch.float32, -7.0),
             "ncand": ((B, T), torch.int32, -77), "counts": ((B, T, S), torch.int32, -77)}
-    bufs = {k: _guarded(*v) for k, v in spec.items()}
-    code = L.gf_e_ransac(p0.data_ptr(), p1.data_ptr(), m0.data_ptr(), th.data_ptr(), B, M, N, T, lo_iters, seed, ws.data_ptr(),
-                         nbytes, *[bufs[k][1].data_ptr() for k in OUT], torch.cuda.current_stream().cuda_stream)
-    lib.check(code, "gf_e_ransac")
-    torch.cuda.synchronize()
-    _intact(ws_buf, 0x5A, "workspace")
-    for k, (buf, _) in bufs.items():
-        _intact(buf, spec[k][2], k)
-    return {k: v[1].clone() for k, v in bufs.items()}
+    return sh.run_once("gf_e_ransac", "gf_e_ws_bytes", B, M, T, spec, lambda ws, nbytes, outs: (
+        p0.data_ptr(), p1.data_ptr(), m0.data_ptr(), th.data_ptr(), B, M, N, T, lo_iters, seed, ws, nbytes, *outs))
 
 
 def ransac(p0, p1, m0, th, T, lo_iters=2, seed=ec.SEED):
     """The raw entry on numpy inputs [B,M,2], [B,N,2], [B,M], [B] (normalised): called twice (equal bits), guards checked."""
     a = (_dev(p0, torch.float32), _dev(p1, torch.float32), _dev(m0, torch.int64), _dev(th, torch.float32))
-    r1, r2 = _ransac_once(*a, T, lo_iters, seed), _ransac_once(*a, T, lo_iters, seed)
-    for k in r1:
-        assert torch.equal(r1[k].view(torch.uint8), r2[k].view(torch.uint8)), f"{k}: two calls differ"
-    out = {k: v.cpu().numpy() for k, v in r1.items()}
-    assert set(np.unique(out["inliers"])) <= {0, 1} and set(np.unique(out["success"])) <= {0, 1}
-    out["inliers"], out["success"] = out["inliers"].astype(bool), out["success"].astype(bool)
-    return out
+    return sh.run_twice(lambda: _ransac_once(*a, T, lo_iters, seed))
 
 
 def _stack(scenes):

@@ -9,65 +9,29 @@ import pytest
 import torch
 
 import h_solver_cases as hc
+import solver_harness as sh
+from solver_harness import dev as _dev, load as _lib
 
 pytestmark = pytest.mark.gpu
 
-G = 64                         # guard elements on either side of every output and of the workspace
 T_FULL = 2 * hc.HYPS + 5       # several workgroups of hypotheses
 K_EDGES = [0, 3, 4, 5, hc.TILE - 1, hc.TILE, hc.TILE + 1]
 T_EDGES = [1, hc.HYPS - 1, hc.HYPS, hc.HYPS + 1, T_FULL]
 
 
-def _lib():
-    from glue_factory_amd import lib
-    return lib, lib.load()
-
-
-def _guarded(shape, dtype, fill):
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * G,), fill, dtype=dtype, device="cuda")
-    return buf, buf[G:G + n].view(shape)
-
-
-def _intact(buf, fill, what):
-    assert bool((buf[:G] == fill).all()) and bool((buf[-G:] == fill).all()), f"guard band of {what} overwritten"
-
-
-def _dev(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda().contiguous()
-
-
 def _ransac_once(kp0, kp1, m0, T, lo_iters, seed, th):
-    lib, L = _lib()
     B, M = m0.shape
     N = kp1.shape[1]
-    nbytes = int(L.gf_h_ws_bytes(B, M, T))
-    assert nbytes > 0 and nbytes % 16 == 0
-    ws_buf, ws = _guarded((nbytes,), torch.uint8, 0x5A)
     spec = {"H": ((B, 3, 3), torch.float32, -7.0), "inliers": ((B, M), torch.uint8, 0xAB), "num": ((B,), torch.int32, -77),
             "success": ((B,), torch.uint8, 0xAB), "samples": ((B, T, 4), torch.int32, -77), "counts": ((B, T), torch.int32, -77)}
-    bufs = {k: _guarded(*v) for k, v in spec.items()}
-    code = L.gf_h_ransac(kp0.data_ptr(), kp1.data_ptr(), m0.data_ptr(), B, M, N, T, th, lo_iters, seed, ws.data_ptr(), nbytes,
-                         *[bufs[k][1].data_ptr() for k in ("H", "inliers", "num", "success", "samples", "counts")],
-                         torch.cuda.current_stream().cuda_stream)
-    lib.check(code, "gf_h_ransac")
-    torch.cuda.synchronize()
-    _intact(ws_buf, 0x5A, "workspace")
-    for k, (buf, _) in bufs.items():
-        _intact(buf, spec[k][2], k)
-    return {k: v[1].clone() for k, v in bufs.items()}
+    return sh.run_once("gf_h_ransac", "gf_h_ws_bytes", B, M, T, spec, lambda ws, nbytes, outs: (
+        kp0.data_ptr(), kp1.data_ptr(), m0.data_ptr(), B, M, N, T, th, lo_iters, seed, ws, nbytes, *outs))
 
 
 def ransac(kp0, kp1, m0, T, lo_iters=2, seed=hc.SEED, th=hc.TH):
     """The raw entry on numpy inputs [B,M,2], [B,N,2], [B,M]: called twice (equal bits), guards checked; numpy outputs."""
     a = (_dev(kp0, torch.float32), _dev(kp1, torch.float32), _dev(m0, torch.int64))
-    r1, r2 = _ransac_once(*a, T, lo_iters, seed, th), _ransac_once(*a, T, lo_iters, seed, th)
-    for k in r1:
-        assert torch.equal(r1[k].view(torch.uint8), r2[k].view(torch.uint8)), f"{k}: two calls differ"
-    out = {k: v.cpu().numpy() for k, v in r1.items()}
-    assert set(np.unique(out["inliers"])) <= {0, 1} and set(np.unique(out["success"])) <= {0, 1}
-    out["inliers"], out["success"] = out["inliers"].astype(bool), out["success"].astype(bool)
-    return out
+    return sh.run_twice(lambda: _ransac_once(*a, T, lo_iters, seed, th))
 
 
 def _stack(scenes):

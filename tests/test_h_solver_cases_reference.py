@@ -17,19 +17,7 @@ REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-# ---- sampling ------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K", [4, 5, 17, hc.TILE + 1])
-def test_samples_are_distinct_and_in_range_and_the_skip_mutation_is_caught(K):
-    s = hc.samples(hc.SEED, 1, 300, K)
-    assert s.min() >= 0 and s.max() < K
-    assert all(len(set(row)) == 4 for row in s.tolist())
-    if K > 4:
-        assert len({tuple(r) for r in s.tolist()}) > 1
-    mutated = hc.samples(hc.SEED, 1, 300, K, off_by_one=True)
-    assert (mutated != s).any()
-    assert any(len(set(row)) < 4 for row in mutated.tolist()) or mutated.max() >= K       # a repeated or out-of-range index
-
-
+# ---- sampling (the distinctness test and its mutation: tests/test_ransac_cases.py, for both sample sizes) -------------------
 def test_small_k_uniformity():
     """Every index of K = 5 is drawn, in every position (a skip mapping that never reaches the last index would not)."""
     s = hc.samples(3, 0, 2000, 5)
