@@ -1,4 +1,4 @@
-// RANSAC skeleton shared by the two-view solvers (h_solver.hip, e_solver.hip): the workspace core, the counter-based
+// RANSAC skeleton shared by the two-view solvers (h_solver.hip, e_solver.hip, hl_solver.hip): the workspace core, the counter-based
 // sampling, the fixed-order block reductions and the winner key, ordered compaction, the tile-streamed inlier count, the flag
 // pass and the rescore, the Hartley-normalised 9 x 9 refit and the flag scatter.  A solver supplies its inlier rule and the
 // rows of its design matrix as functors and keeps its own __global__ kernels: one workgroup of 256 lanes per pair, except
@@ -18,6 +18,9 @@
 // Refit: fp64 throughout.  Hartley normalisation over the kept correspondences (centroid, mean distance sqrt 2), the 45
 // distinct sums of the normal matrix through a fixed-order block reduction, cyclic Jacobi sweeps on the 9 x 9 matrix in LDS
 // (gf_jacobi9.h), the eigenvector of the smallest eigenvalue, de-normalisation on the view-0 side.
+//
+// Two-part feature lists (hl_solver.hip): a second ordered list, of line matches, behind the point matches; its compaction,
+// tile-streamed count, flag pass, rescore and scatter are templates of their own below, beside the one-list ones.
 #pragma once
 #include "gf_common.h"
 #include "gf_amd.h"
@@ -257,6 +260,149 @@ __device__ __forceinline__ void scatter_flags(const RansacWs& w, int b, int M, b
     const int K = w.K[b];
     for (int k = tid; k < K; k += 256)
         if (w.flags[(int64_t)b * M + k]) inliers[(int64_t)b * M + w.idx[(int64_t)b * M + k]] = 1;
+}
+
+// ---- two-part feature lists (hl_solver.hip): ordered point matches first, then ordered line matches --------------------------
+// The line part of a workspace whose point part is a RansacWs.  A line match is two view-0 endpoints p, q and two view-1
+// endpoints r, s: seg[2 k] = (px, py, qx, qy), seg[2 k + 1] = (rx, ry, sx, sy); line[k] = (a, b, c, 0) is the view-1 line through
+// r and s in pixels with a^2 + b^2 = 1.
+struct LineWs {
+    int* K;                     // [B] line matches of the pair
+    int* idx;                   // [B, L] ordered indices of the matched segments of view 0
+    float4* seg;                // [B, 2 L] endpoints of the ordered line matches
+    float4* line;               // [B, L] unit-normal view-1 lines of the ordered line matches
+    uint8_t* flags;             // [B, L] inlier flags of the current model over the ordered line matches
+};
+constexpr int ST_LINES = 3;      // state word: the line inliers among ST_COUNT (two-part solvers only)
+
+inline void carve_lines(Carver& c, int B, int L, LineWs& w) {
+    w.K = c.take<int>((size_t)B);
+    w.idx = c.take<int>((size_t)B * L);
+    w.seg = c.take<float4>(2 * (size_t)B * L);
+    w.line = c.take<float4>((size_t)B * L);
+    w.flags = c.take<uint8_t>((size_t)B * L);
+}
+
+// ordered compaction of the line matches of pair b (ascending i), as compact_pair orders the points; a match index outside
+// [0, L1), a non-finite coordinate or a segment shorter than eps_len pixels in either view counts as no match
+__device__ __forceinline__ void compact_lines(const float* l0, const float* l1, const int64_t* lm0, const LineWs& w, int b, int L,
+                                              int L1, double eps_len, int* wsum /* [4] */) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int base = 0;
+    for (int i0 = 0; i0 < L; i0 += 256) {
+        const int i = i0 + tid;
+        const int64_t j = i < L ? lm0[(int64_t)b * L + i] : -1;
+        bool f = j >= 0 && j < L1;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), c = a, ln = a;
+        if (f) {
+            const float* p = l0 + ((int64_t)b * L + i) * 4;
+            const float* r = l1 + ((int64_t)b * L1 + j) * 4;
+            a = make_float4(p[0], p[1], p[2], p[3]);
+            c = make_float4(r[0], r[1], r[2], r[3]);
+            const double dx0 = (double)a.z - a.x, dy0 = (double)a.w - a.y, dx1 = (double)c.z - c.x, dy1 = (double)c.w - c.y;
+            const double n0 = dx0 * dx0 + dy0 * dy0, n1 = dx1 * dx1 + dy1 * dy1;
+            f = isfinite(n0) && isfinite(n1) && n0 >= eps_len * eps_len && n1 >= eps_len * eps_len;   // a NaN compares false
+            const double inv = 1. / sqrt(n1);
+            ln = make_float4((float)(-dy1 * inv), (float)(dx1 * inv), (float)(((double)c.x * c.w - (double)c.z * c.y) * inv), 0.f);
+        }
+        const unsigned long long mask = __ballot(f);
+        const int pre = __popcll(mask & ((1ull << lane) - 1ull));
+        if (lane == 0) wsum[wv] = __popcll(mask);
+        __syncthreads();
+        int off = base;
+        for (int q = 0; q < wv; ++q) off += wsum[q];
+        const int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (f) {
+            const int64_t at = (int64_t)b * L + off + pre;
+            w.idx[at] = i;
+            w.seg[2 * at] = a;
+            w.seg[2 * at + 1] = c;
+            w.line[at] = ln;
+        }
+        base += tot;
+        __syncthreads();
+    }
+    if (tid == 0) w.K[b] = base;
+}
+
+// tile_count for the line part: view-0 endpoints and view-1 lines stream through two LDS tiles, broadcast reads.
+// inlier(model, endpoints, line, th) is the solver's rule
+template <int TILE, typename Inlier>
+__device__ __forceinline__ int tile_count_lines(const float* model, const float4* seg, const float4* line, int K, float th,
+                                                float4* tile_e, float4* tile_l, Inlier inlier) {
+    int count = 0;
+    for (int k0 = 0; k0 < K; k0 += TILE) {
+        const int n = min(TILE, K - k0);
+        __syncthreads();
+        for (int k = threadIdx.x; k < n; k += 256) { tile_e[k] = seg[2 * (k0 + k)]; tile_l[k] = line[k0 + k]; }
+        __syncthreads();
+        for (int k = 0; k < n; ++k) count += inlier(model, tile_e[k], tile_l[k], th) ? 1 : 0;
+    }
+    return count;
+}
+
+// flag_pass for the line part
+template <typename Inlier>
+__device__ __forceinline__ int flag_pass_lines(const float* model, const float4* seg, const float4* line, uint8_t* flags, int K,
+                                               float th, int* red, Inlier inlier) {
+    int count = 0;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const bool in = inlier(model, seg[2 * k], line[k], th);
+        if (flags != nullptr) flags[k] = in ? 1 : 0;
+        count += in ? 1 : 0;
+    }
+    return block_sum_int(count, red);
+}
+
+// set_current over both parts: ST_COUNT is the total, ST_LINES the line share
+template <typename PointInlier, typename LineInlier>
+__device__ __forceinline__ void set_current2(const RansacWs& w, const LineWs& wl, int b, int M, int L, const float* model,
+                                             const float* kept, bool ok, float th, int* red, PointInlier pin, LineInlier lin) {
+    const int tid = threadIdx.x;
+    const int np = flag_pass(model, w.corr + (int64_t)b * M, w.flags + (int64_t)b * M, w.K[b], th * th, red, pin);
+    const int nl = flag_pass_lines(model, wl.seg + 2 * (int64_t)b * L, wl.line + (int64_t)b * L, wl.flags + (int64_t)b * L,
+                                   wl.K[b], th, red, lin);
+    if (tid < 9) w.cur[(int64_t)b * 12 + tid] = kept[tid];
+    if (tid == 0) {
+        w.state[b * 4 + ST_COUNT] = np + nl;
+        w.state[b * 4 + ST_LINES] = nl;
+        w.state[b * 4 + ST_CUR_OK] = ok ? 1 : 0;
+        w.state[b * 4 + ST_REFIT_OK] = 0;
+    }
+}
+
+// rescore_pair over both parts: the refit replaces the current model when it is valid and the total count does not drop
+template <typename PointInlier, typename LineInlier>
+__device__ __forceinline__ void rescore_pair2(const RansacWs& w, const LineWs& wl, int b, int M, int L, float th, int* red,
+                                              PointInlier pin, LineInlier lin) {
+    const int tid = threadIdx.x;
+    if (w.state[b * 4 + ST_CUR_OK] == 0 || w.state[b * 4 + ST_REFIT_OK] == 0) return;       // uniform
+    const int Kp = w.K[b], Kl = wl.K[b];
+    const float4* corr = w.corr + (int64_t)b * M;
+    const float4* seg = wl.seg + 2 * (int64_t)b * L;
+    const float4* line = wl.line + (int64_t)b * L;
+    float model[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) model[i] = w.refit[(int64_t)b * 12 + i];
+    const int np = flag_pass(model, corr, nullptr, Kp, th * th, red, pin);
+    const int nl = flag_pass_lines(model, seg, line, nullptr, Kl, th, red, lin);
+    if (np + nl < w.state[b * 4 + ST_COUNT]) return;                                        // uniform
+    flag_pass(model, corr, w.flags + (int64_t)b * M, Kp, th * th, red, pin);
+    flag_pass_lines(model, seg, line, wl.flags + (int64_t)b * L, Kl, th, red, lin);
+    __syncthreads();
+    if (tid < 9) w.cur[(int64_t)b * 12 + tid] = model[tid];
+    if (tid == 0) { w.state[b * 4 + ST_COUNT] = np + nl; w.state[b * 4 + ST_LINES] = nl; }
+}
+
+// scatter_flags for the line part: line_inliers[b, :] over the segments of view 0
+__device__ __forceinline__ void scatter_line_flags(const LineWs& wl, int b, int L, bool ok, uint8_t* line_inliers) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < L; i += 256) line_inliers[(int64_t)b * L + i] = 0;
+    __syncthreads();
+    if (!ok) return;
+    const int K = wl.K[b];
+    for (int k = tid; k < K; k += 256)
+        if (wl.flags[(int64_t)b * L + k]) line_inliers[(int64_t)b * L + wl.idx[(int64_t)b * L + k]] = 1;
 }
 
 // ---- refit ------------------------------------------------------------------------------------------------------------------

@@ -91,6 +91,8 @@ SIGNATURES = {
     "gf_h_ws_bytes": [_I, _I, _I],
     "gf_h_ransac": [_P, _P, _P, _I, _I, _I, _I, _F, _I, _c.c_uint32, _P, _L] + [_P] * 7,
     "gf_h_dlt": [_P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P],
+    "gf_hl_ws_bytes": [_I, _I, _I, _I],
+    "gf_hl_ransac": [_P] * 6 + [_I] * 6 + [_F, _I, _c.c_uint32, _P, _L] + [_P] * 9,
     "gf_e_ws_bytes": [_I, _I, _I],
     "gf_e_ransac": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _c.c_uint32, _P, _L] + [_P] * 11,
     "gf_e_pose": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _P],
@@ -119,7 +121,7 @@ SIGNATURES = {
     "gf_ln_gelu_nblk": [_I],
     "gf_ln_gelu_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
 }
-_RESTYPE = {"gf_h_ws_bytes": _c.c_int64, "gf_e_ws_bytes": _c.c_int64, "gf_sinkhorn_ws_bytes": _c.c_int64, "gf_linear_dw_ws_bytes": _c.c_int64}
+_RESTYPE = {"gf_h_ws_bytes": _c.c_int64, "gf_hl_ws_bytes": _c.c_int64, "gf_e_ws_bytes": _c.c_int64, "gf_sinkhorn_ws_bytes": _c.c_int64, "gf_linear_dw_ws_bytes": _c.c_int64}
 
 _lib = None
 

@@ -4,7 +4,8 @@ Restates gluefactory/models/utils/metrics.py:4-50 (recall, precision, accuracy a
 ranking average precision of matches0 against gt_matches0); tiny tensors, stock torch ops.
 
 Homography evaluation (gluefactory/geometry/homography.py:314-342, gluefactory/eval/utils.py:137-156, 197-261), batched:
-sym_homography_error, homography_corner_error and homography_metrics, the last on top of the GPU solvers of ``solvers/``.
+sym_homography_error, homography_corner_error and homography_metrics, the last on top of the GPU solvers of ``solvers/``;
+point_line_homography_metrics adds the line inliers of the point-and-line solver.
 
 Relative-pose evaluation (gluefactory/geometry/epipolar.py:127-155, gluefactory/utils/tools.py:137-149,
 gluefactory/eval/utils.py:41-70, 159-194), batched: relative_pose_error, pose_auc and relative_pose_metrics."""
@@ -107,6 +108,28 @@ def homography_metrics(pred, data):
             out["ransac_inl"] = ninl
             out["ransac_inl%"] = ninl / nm.clamp(min=1)
     return out
+
+
+@torch.no_grad()
+def point_line_homography_metrics(pred, data):
+    """homography_metrics for a prediction that carries the point-and-line solver's output (solvers.
+    point_line_homography_ransac): the same values, plus ``ransac_line_inl`` (the line inliers of the model) and
+    ``ransac_line_inl%`` (their share of the line matches; 0 without line matches), where ``pred`` has ``line_inliers``.
+    Every value is a [B] tensor."""
+    return {**homography_metrics(pred, data), **line_inlier_metrics(pred)}
+
+
+@torch.no_grad()
+def line_inlier_metrics(pred):
+    """The line part of point_line_homography_metrics (plain tensor arithmetic on any device): {} without ``line_inliers``."""
+    if "line_inliers" not in pred:
+        return {}
+    ninl = pred["line_inliers"].float().sum(1)
+    if "line_matches0" in pred and pred["line_matches0"].shape == pred["line_inliers"].shape:
+        nlm = (pred["line_matches0"] > -1).sum(1)
+    else:
+        nlm = torch.zeros_like(ninl, dtype=torch.long)
+    return {"ransac_line_inl": ninl, "ransac_line_inl%": ninl / nlm.clamp(min=1)}
 
 
 # ---------------------------------------------------------------------------------------------- relative-pose evaluation

@@ -543,6 +543,42 @@ int gf_h_ransac(const float* kpts0, const float* kpts1, const int64_t* matches0,
 int gf_h_dlt(const float* kpts0, const float* kpts1, const int64_t* matches0, const float* weights, int B, int M, int N,
              void* ws, int64_t ws_bytes, float* H, uint8_t* success, void* stream);
 
+/* ---- point-and-line homography solver (csrc/hl_solver.hip, csrc/hl_fit.h).  Additive: ABI 20 unchanged.
+ * Batched RANSAC whose hypotheses are drawn from point matches, line matches or a mix of both, with a Hartley-normalised DLT
+ * refit over both kinds.  It fills the place of gluefactory/robust_estimators/homography/homography_est.py (the hybrid
+ * estimator behind `estimator: homography_est`, fed m_lines0 / m_lines1 by gluefactory/eval/utils.py:197-238).  That
+ * estimator is a CPU package this project cannot install; nothing was compared against it, and the semantics stated in the
+ * header comments of csrc/hl_solver.hip and csrc/hl_fit.h are the DEFINITION of this solver.  tests/hl_solver_cases.py
+ * restates them on the host.  Kernel nodes only, nothing allocated, no environment read, no host synchronisation; rejected
+ * arguments return an error code before anything is enqueued.
+ * Inputs: kpts0 [B,M,2], kpts1 [B,N,2] fp32, matches0 [B,M] int64 (an index outside [0, N) means no match); lines0 [B,L,2,2],
+ * lines1 [B,L1,2,2] fp32 segments as two (x, y) endpoints, line_matches0 [B,L] int64 (an index outside [0, L1) means no
+ * match; so does a non-finite coordinate or a segment shorter than GF_HL_EPS_LEN pixels in either view).  Either list may be
+ * empty: M == 0 or L == 0 is legal and the pointers of an empty list (its inputs and its inlier output) may then be NULL and
+ * N or L1 anything; M == 0 and L == 0 together is GF_ERR_SHAPE.  ws: gf_hl_ws_bytes(B, M, L, T) bytes of device scratch,
+ * 16-byte aligned (GF_ERR_ALIGN); ws_bytes = the size the caller really holds (GF_ERR_SHAPE when too small).  B <= 0, M < 0,
+ * L < 0, N <= 0 with M > 0, L1 <= 0 with L > 0, T < 1, a NULL required pointer, ransac_th not in (0, 1e18), lo_iters outside
+ * [0, 64]: GF_ERR_SHAPE.
+ * gf_hl_ransac: T hypotheses per pair, each from 4 features drawn over the K_p ordered point matches followed by the K_l
+ *   ordered line matches, all evaluated (no early exit); the winner has the highest integer count of point inliers + line
+ *   inliers, ties to the lowest hypothesis index; lo_iters rounds of {DLT refit on the current inliers of both kinds, rescore,
+ *   accept when the total does not drop}.  4 + 2 lo_iters launches whatever B, the counts and the data.  H [B,3,3] fp32 with
+ *   H[2][2] == 1 (identity where success is 0), inliers [B,M] one byte per keypoint of view 0, line_inliers [B,L] one byte per
+ *   segment of view 0, num_inliers [B,2] int32 (points, lines), success [B] one byte.  Debug outputs (each may be NULL):
+ *   samples [B,T,4] int32, indices into the pair's ordered feature list (-1 where K_p + K_l < 4); hyp_H [B,T,9] fp32, the
+ *   model of every hypothesis (zero where rejected); hyp_counts [B,T,2] int32 (points, lines; -1 where rejected). */
+#define GF_HL_TILE 256        /* point matches, then line matches, per LDS tile of the scoring kernel */
+#define GF_HL_HYPS 256        /* hypotheses per workgroup of the scoring kernel (one per lane) */
+#define GF_HL_EPS_LEN 1.0f    /* a line match is dropped when either of its segments is shorter than this (pixels) */
+#define GF_HL_EPS_PIVOT 1e-9  /* a sample is rejected when a pivot of its 8 x 9 elimination is below this (conditioned rows of unit scale) */
+#define GF_HL_H22_FRAC 1e-4f  /* a model is rejected when |h22| < GF_HL_H22_FRAC ||H||_F (as GF_H_H22_FRAC) */
+#define GF_HL_JACOBI 12       /* cyclic Jacobi sweeps of the 9 x 9 eigenproblem of the refit (as GF_H_JACOBI) */
+int64_t gf_hl_ws_bytes(int B, int M, int L, int T);
+int gf_hl_ransac(const float* kpts0, const float* kpts1, const int64_t* matches0, const float* lines0, const float* lines1,
+                 const int64_t* line_matches0, int B, int M, int N, int L, int L1, int T, float ransac_th, int lo_iters,
+                 uint32_t seed, void* ws, int64_t ws_bytes, float* H, uint8_t* inliers, uint8_t* line_inliers,
+                 int32_t* num_inliers, uint8_t* success, int32_t* samples, float* hyp_H, int32_t* hyp_counts, void* stream);
+
 /* ---- relative-pose solver (csrc/e_solver.hip, csrc/e_fivept.h).  Additive: ABI 20 unchanged.
  * Batched 5-point RANSAC, eight-point refit and pose recovery on the GPU, standing in for
  * gluefactory/robust_estimators/relative_pose/opencv.py:23-64 (cv2.findEssentialMat on normalised coordinates with the
