@@ -96,6 +96,8 @@ SIGNATURES = {
     "gf_e_ws_bytes": [_I, _I, _I],
     "gf_e_ransac": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _c.c_uint32, _P, _L] + [_P] * 11,
     "gf_e_pose": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _P],
+    "gf_hv_warp": [_P, _I, _P, _P, _P, _P, _P] + [_I] * 10 + [_P],
+    "gf_hv_filter": [_P] * 6 + [_I] * 6 + [_P],
     "gf_bias_act_bn_nhwc": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "gf_conv1_bias_act_bn": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "gf_conv3x3_c64": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],

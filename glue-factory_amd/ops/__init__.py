@@ -41,3 +41,6 @@ FOLD_ENABLED = True      # tools/probe/ab_matcher.py switches it off for a same-
 REPLAY_GATE = None
 
 FORCE_SYNC_BN = False     # tests: take the SyncBatchNorm exchange in a one-rank group too (TrainStep(force_distributed=True))
+
+# data-preparation kernels (csrc/hviews.hip): not autograd ops; their wrappers live with the stage that uses them
+from ..data._views_ops import filter_views, warp_views  # noqa: E402

@@ -619,6 +619,46 @@ int gf_e_ransac(const float* pts0n, const float* pts1n, const int64_t* matches0,
 int gf_e_pose(const float* pts0n, const float* pts1n, const int64_t* matches0, const uint8_t* inliers, const float* E, int B,
               int M, int N, void* ws, int64_t ws_bytes, float* R, float* t, int32_t* num_front, void* stream);
 
+/* ---- homography view synthesis (csrc/hviews.hip).  Additive: ABI 20 unchanged.
+ * V output views from S source images on the GPU, standing in for the per-view cv2.warpPerspective + albumentations chain +
+ * grayscale of gluefactory/datasets/homographies.py:37-44, :217-233.  The photometric stages are this project's own float
+ * formulation (no uint8 round trip); which transforms of the reference's presets they cover is listed in
+ * glue_factory_amd/data/homography_views.py.  Kernel nodes only, nothing allocated, no environment read, no host
+ * synchronisation; rejected arguments return an error code before anything is enqueued.  The arithmetic of both kernels, with the
+ * order of every fmaf, is written down in the header comment of csrc/hviews.hip; tests/homography_views_cases.py restates it.
+ * gf_hv_warp: src [S,Hmax,Wmax,C] NHWC, C in {1,3}, src_dtype GF_DTYPE_U8 (values / 255) or GF_DTYPE_F32; src_sizes [S,2] int32
+ *   (w, h) = each source's own size, both <= the padded extents: a tap outside the OWN size contributes 0 (cv2's constant
+ *   border) and the padding is never read; view_src [V] int32 = the source of each view, any order, repeats allowed;
+ *   Hinv [V,9] fp32 row major, patch pixel -> source pixel, pixel centres at integer coordinates; params [V,GF_HV_NPARAM] fp32 =
+ *   (gamma, value shift, a, b); out [V,Cout,ph,pw] fp32.  Per pixel: perspective division in fp32; sampled value 0 when the
+ *   denominator d is not finite, |d| < GF_HV_EPS_D or the source position lies outside [-1, w] x [-1, h]; else bilinear on floorf
+ *   with four taps; PRE stage: powf(v, gamma) when gamma != 1, then the value shift s (C = 1: clamp(v + s, 0, 1); C = 3: with
+ *   m = max(r, g, b) > 0 every channel times clamp(m + s, 0, 1) / m); with finish != 0 also the POST stage clamp(a v + b, 0, 1)
+ *   and, with gray != 0 and C = 3, the single channel 0.299 r + 0.587 g + 0.114 b.  Cout must be 1 when finish and gray are
+ *   both set and C otherwise (gray without finish is carried out by gf_hv_filter).
+ * gf_hv_filter: in [V,C,ph,pw] fp32 -> out [V,Cout,ph,pw] (not in place); tap_off [V,GF_HV_MAXTAPS,2] int32 (dx, dy) with
+ *   |dx|, |dy| <= GF_HV_RADIUS, tap_w [V,GF_HV_MAXTAPS] fp32, ntaps [V] int32 in [1, GF_HV_MAXTAPS].
+ *   out(x, y) = sum_t w_t in(x + dx_t, y + dy_t) (correlation; an fp32 fmaf chain in tap order starting from 0), border
+ *   reflect-101, then the POST stage and gray exactly as above (Cout = 1 with gray, else C).  An unblurred view carries the
+ *   single tap (0, 0, 1), which passes bits through; there is no special case.
+ * Checked on the host (GF_ERR_SHAPE): a NULL pointer, S, Hmax, Wmax, V, ph, pw <= 0, C not in {1,3}, a Cout that does not
+ *   follow from C, finish and gray, V or the number of 16-row tiles above 65535, for the filter ph or pw <= GF_HV_RADIUS and
+ *   in == out; a src_dtype other than the two above is GF_ERR_DTYPE.
+ * The tables live in device memory and are NOT read on the host.  The kernels clamp instead, so that no table value can make
+ *   them touch memory outside the buffers: view_src to [0, S), src_sizes to [0, Wmax] x [0, Hmax], ntaps to [1, GF_HV_MAXTAPS],
+ *   every tap offset to [-GF_HV_RADIUS, GF_HV_RADIUS].  Callers that build the tables on the host validate them there
+ *   (glue_factory_amd.data.homography_views.check_tables raises on exactly these ranges). */
+#define GF_DTYPE_U8 2          /* gf_hv_warp's src_dtype only */
+#define GF_HV_NPARAM 4         /* floats per view of `params`: gamma, value shift, a, b */
+#define GF_HV_MAXTAPS 81       /* taps per view: a 9 x 9 box */
+#define GF_HV_RADIUS 12        /* largest |dx|, |dy|: a 25-pixel motion line */
+#define GF_HV_EPS_D 1e-8f      /* the sampled value is 0 where the perspective denominator is smaller than this in magnitude */
+int gf_hv_warp(const void* src, int src_dtype, const int32_t* src_sizes, const int32_t* view_src, const float* Hinv,
+               const float* params, float* out, int S, int Hmax, int Wmax, int C, int V, int Cout, int ph, int pw, int finish,
+               int gray, void* stream);
+int gf_hv_filter(const float* in, const int32_t* tap_off, const float* tap_w, const int32_t* ntaps, const float* params,
+                 float* out, int V, int C, int Cout, int ph, int pw, int gray, void* stream);
+
 /* ---- frozen SuperPoint extractor tails (gluefactory/models/extractors/superpoint_open.py; the
  * convolutions stay on the stock library).
  * gf_bias_act_bn_nhwc: one pass for the VGGBlock tail Conv2d(no bias) -> +bias -> ReLU -> BatchNorm2d(eval)
