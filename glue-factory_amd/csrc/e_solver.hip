@@ -9,9 +9,10 @@
 // lo_iters x (refit, rescore), pose; 2 for gf_e_pose: compact, pose).  Nothing depends on a count the host reads: every
 // kernel takes its pair's match count K_b from the workspace.
 //
-// The RANSAC machinery (workspace core, sampling, reductions and the winner key, compaction, the tile-streamed count, flag
-// pass, rescore, the skeleton of the refit, flag scatter) is ransac_common.h, shared with h_solver.hip; what is here is the
-// model: the 5-point solve, the Sampson rule, the rows and the view-1 side of the eight-point fit, the pose.
+// The RANSAC machinery (workspace core, sampling, reductions and the winner key, compaction, the feature parts with the
+// tile-streamed count, flag pass and rescore over them, the skeleton of the refit, flag scatter) is ransac_common.h, shared
+// with h_solver.hip and hl_solver.hip; what is here is the model: the 5-point solve, the Sampson rule, the rows and the
+// view-1 side of the eight-point fit, the pose.
 //
 // Sampling: five draws per hypothesis by the rule in the header of ransac_common.h.
 //
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(256) void e_score_kernel(Ws w, const float* th, int
     if (ci < T * MAXSOL) ok = (ci % MAXSOL) < w.ncand[(int64_t)b * T + ci / MAXSOL];
 #pragma unroll
     for (int i = 0; i < 9; ++i) E[i] = ok ? w.cand[((int64_t)b * T * MAXSOL + ci) * 9 + i] : 0.f;   // zero: no inlier
-    const int count = tile_count<TILE>(E, corr, K, th2, tile, Inlier());
+    const int count = tile_count<TILE>(E, PointPart{corr, nullptr, K, th2}, tile, Inlier());
     if (cand_counts != nullptr && ci < T * MAXSOL) cand_counts[(int64_t)b * T * MAXSOL + ci] = ok ? count : -1;
     const unsigned long long m = block_max_key(pack_key(ok, count, ci), red);
     if (tid == 0) w.best[(int64_t)b * nblk + blk] = m;
@@ -133,15 +134,15 @@ __global__ __launch_bounds__(256) void e_select_kernel(Ws w, const float* th, in
     __shared__ unsigned long long red[4];
     __shared__ int ired[4];
     const int b = blockIdx.x;
-    const int K = w.K[b];
-    const float thb = th[b], th2 = thb * thb;
+    const float thb = th[b];
+    const PointPart part = point_part(w, b, M, thb * thb);
     const unsigned long long m = pair_max_key(w, b, nblk, red);
-    const bool ok = m != 0ull && K >= 5;
+    const bool ok = m != 0ull && part.K >= 5;
     float E[9];
     const int64_t ci = ok ? (int64_t)key_index(m) : 0;
 #pragma unroll
     for (int i = 0; i < 9; ++i) E[i] = ok ? w.cand[((int64_t)b * T * MAXSOL + ci) * 9 + i] : 0.f;   // zero flags nothing
-    set_current(w, b, M, K, E, E, ok, th2, ired, Inlier());
+    set_current(w, b, E, E, ok, ired, Inlier(), part);
 }
 
 // Hartley-normalised eight-point fit over the flagged matches, projected onto the essential manifold -> refit,
@@ -158,18 +159,20 @@ __global__ __launch_bounds__(256) void e_refit_kernel(Ws w, int M) {
         if (tid == 0) w.state[b * 4 + ST_REFIT_OK] = 0;
         return;
     }
-    auto keep = [&](int k) { return flags[k] != 0; };
+    const auto part = point_refit(
+        corr, K, [=](int k) { return flags[k] != 0; },
+        [](double (&acc)[45], int, double x, double y, double u, double v) {
+            const double r[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.};
+            int at = 0;
+#pragma unroll
+            for (int i = 0; i < 9; ++i)
+#pragma unroll
+                for (int j = i; j < 9; ++j) { acc[at] += r[i] * r[j]; ++at; }
+        });
     Hartley t;
-    refit_centroids(corr, K, red, t, keep);
+    refit_moments(red, t, part);
     double m[9];
-    refit_solve(corr, K, red, A, V, GF_E_JACOBI, t, m, keep, [&](double (&acc)[45], int, double x, double y, double u, double v) {
-        const double r[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.};
-        int at = 0;
-#pragma unroll
-        for (int i = 0; i < 9; ++i)
-#pragma unroll
-            for (int j = i; j < 9; ++j) { acc[at] += r[i] * r[j]; ++at; }
-    });
+    refit_solve(red, A, V, GF_E_JACOBI, t, m, part);
     if (tid == 0) {
         // E = T1^T (G T0) with T1 = [[s1, 0, -s1 cx1], [0, s1, -s1 cy1], [0, 0, 1]]
         double e[9];
@@ -189,7 +192,8 @@ __global__ __launch_bounds__(256) void e_refit_kernel(Ws w, int M) {
 __global__ __launch_bounds__(256) void e_rescore_kernel(Ws w, const float* th, int M) {
     __shared__ int ired[4];
     const int b = blockIdx.x;
-    rescore_pair(w, b, M, [=]() { const float thb = th[b]; return thb * thb; }, ired, Inlier());
+    const float thb = th[b];
+    rescore_pair(w, b, ired, Inlier(), point_part(w, b, M, thb * thb));
 }
 
 // pose of the model by the depth test, and the outputs.  ransac != 0: the current model and its flags from the workspace,
@@ -250,7 +254,7 @@ __global__ __launch_bounds__(256) void e_pose_kernel(Ws w, int M, int ransac, co
         success[b] = ok ? 1 : 0;
         num_inliers[b] = ok ? w.state[b * 4 + ST_COUNT] : 0;
     }
-    scatter_flags(w, b, M, ok, inliers);
+    scatter_flags(w.flags + (int64_t)b * M, idx, K, M, ok, inliers + (int64_t)b * M);
 }
 
 inline int check_common(const void* p0, const void* p1, const void* m0, int B, int M, int N, int T, const void* ws,

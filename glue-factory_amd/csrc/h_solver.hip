@@ -8,9 +8,10 @@
 // lanes per pair except the scoring kernel (one workgroup per GF_H_HYPS hypotheses of a pair).  Nothing depends on a count
 // the host reads: every kernel takes its pair's match count K_b from the workspace.
 //
-// The RANSAC machinery (workspace core, sampling, reductions and the winner key, compaction, the tile-streamed count, flag
-// pass, rescore, the skeleton of the refit, flag scatter) is ransac_common.h, shared with e_solver.hip; what is here is the
-// model: the 4-point fit, the inlier rule, the rows and the view-1 side of the DLT, and the kernels' names.
+// The RANSAC machinery (workspace core, sampling, reductions and the winner key, compaction, the feature parts with the
+// tile-streamed count, flag pass and rescore over them, the skeleton of the refit, flag scatter) is ransac_common.h, shared
+// with e_solver.hip and hl_solver.hip; the inlier rule, the rows and the view-1 side of the DLT are h_model.h, shared with
+// hl_solver.hip; what is here is the rest of the model: the 4-point fit, the gates of the refit, and the kernels' names.
 //
 // Sampling: four draws per hypothesis by the rule in the header of ransac_common.h.
 //
@@ -28,7 +29,7 @@
 //
 // Refit: the skeleton of ransac_common.h over the flagged correspondences (the weights do not enter the normalisation, as in
 // kornia) with the two rows per correspondence of A^T W A and GF_H_JACOBI sweeps, then H = T1^-1 G T0 and h22 = 1.
-#include "ransac_common.h"
+#include "h_model.h"
 
 namespace {
 
@@ -103,16 +104,6 @@ __device__ __forceinline__ bool fit4(const float4 c[4], float h[9]) {
     return ok;
 }
 
-struct Inlier {
-    __device__ __forceinline__ bool operator()(const float* h, float4 c, float th2) const {
-        const float w = h[6] * c.x + h[7] * c.y + h[8];
-        const float iw = 1.f / w;
-        const float dx = (h[0] * c.x + h[1] * c.y + h[2]) * iw - c.z;
-        const float dy = (h[3] * c.x + h[4] * c.y + h[5]) * iw - c.w;
-        return (w > 0.f) && isfinite(w) && (dx * dx + dy * dy < th2);      // a NaN error compares false
-    }
-};
-
 // ---- kernels ----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void h_compact_kernel(const float* kp0, const float* kp1, const int64_t* m0, Ws w,
                                                         int M, int N) {
@@ -151,7 +142,7 @@ __global__ __launch_bounds__(256) void h_score_kernel(Ws w, int M, int T, int nb
 #pragma unroll
         for (int d = 0; d < 4; ++d) sp[d] = s[d];
     }
-    const int count = tile_count<TILE>(h, corr, K, th2, tile, Inlier());
+    const int count = tile_count<TILE>(h, PointPart{corr, nullptr, K, th2}, tile, TransferInlier());
     if (hyp_counts != nullptr && t < T) hyp_counts[(int64_t)b * T + t] = ok ? count : -1;
     const unsigned long long m = block_max_key(pack_key(ok, count, t), red);
     if (tid == 0) w.best[(int64_t)b * nblk + blk] = m;
@@ -164,14 +155,15 @@ __global__ __launch_bounds__(256) void h_select_kernel(Ws w, int M, int nblk, fl
     __shared__ float hs[9];
     __shared__ int oks;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int K = w.K[b];
+    const PointPart part = point_part(w, b, M, th2);
+    const int K = part.K;
     const unsigned long long m = pair_max_key(w, b, nblk, red);
     if (tid == 0) {
         float h[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
         bool ok = false;
         int s[4];
         if (m != 0ull && K >= 4)                                  // the same arithmetic as the scoring lane's
-            ok = sample_fit(seed, b, key_index(m), K, w.corr + (int64_t)b * M, s, h);
+            ok = sample_fit(seed, b, key_index(m), K, part.corr, s, h);
         for (int i = 0; i < 9; ++i) hs[i] = ok ? h[i] : (i % 4 == 0 ? 1.f : 0.f);
         oks = ok ? 1 : 0;
     }
@@ -180,7 +172,7 @@ __global__ __launch_bounds__(256) void h_select_kernel(Ws w, int M, int nblk, fl
     float h[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) h[i] = ok ? hs[i] : 0.f;          // an all-zero model flags nothing
-    set_current(w, b, M, K, h, hs, ok, th2, ired, Inlier());
+    set_current(w, b, h, hs, ok, ired, TransferInlier(), part);
 }
 
 // Hartley-normalised weighted DLT over the flagged matches (use_flags == 0: over all of them) -> refit, state[ST_REFIT_OK]
@@ -192,48 +184,28 @@ __global__ __launch_bounds__(256) void h_refit_kernel(Ws w, const float* weights
     const uint8_t* flags = w.flags + (int64_t)b * M;
     const int* idx = w.idx + (int64_t)b * M;
     float* Hn = w.refit + (int64_t)b * 12;
+    int* refit_ok = w.state + b * 4 + ST_REFIT_OK;
     // gate: refit only where the pair has a current model (the local optimisation of gf_h_ransac); else nothing is kept
     const int K = (gate == 0 || w.state[b * 4 + ST_CUR_OK] != 0) ? w.K[b] : 0;
-    auto keep = [&](int k) { return !use_flags || flags[k]; };
+    const auto part = point_refit(
+        corr, K, [=](int k) { return !use_flags || flags[k]; },
+        [=](double (&acc)[45], int k, double x, double y, double u, double v) {
+            add_point_rows<true>(acc, x, y, u, v, weights != nullptr ? (double)weights[(int64_t)b * M + idx[k]] : 1.);
+        });
     Hartley t;
-    refit_centroids(corr, K, red, t, keep);
+    refit_moments(red, t, part);
     if (!(t.n >= 4.)) {                                             // uniform over the workgroup
-        if (tid < 9) Hn[tid] = (tid % 4 == 0) ? 1.f : 0.f;
-        if (tid == 0) w.state[b * 4 + ST_REFIT_OK] = 0;
+        h_refit_none(Hn, refit_ok);
         return;
     }
     double m[9];
-    refit_solve(corr, K, red, A, V, GF_H_JACOBI, t, m, keep, [&](double (&acc)[45], int k, double x, double y, double u, double v) {
-        const double wt = weights != nullptr ? (double)weights[(int64_t)b * M + idx[k]] : 1.;
-        const double r0[9] = {0., 0., 0., -x, -y, -1., v * x, v * y, v};
-        const double r1[9] = {x, y, 1., 0., 0., 0., -u * x, -u * y, -u};
-        int at = 0;
-#pragma unroll
-        for (int i = 0; i < 9; ++i)
-#pragma unroll
-            for (int j = i; j < 9; ++j) { acc[at] += wt * (r0[i] * r0[j] + r1[i] * r1[j]); ++at; }
-    });
-    if (tid == 0) {
-        // H = T1^-1 (G T0) with T1^-1 = [[1/s1, 0, cx1], [0, 1/s1, cy1], [0, 0, 1]]
-        double hh[9];
-        for (int c = 0; c < 3; ++c) {
-            hh[0 + c] = m[0 + c] / t.sc1 + t.cx1 * m[6 + c];
-            hh[3 + c] = m[3 + c] / t.sc1 + t.cy1 * m[6 + c];
-            hh[6 + c] = m[6 + c];
-        }
-        double fro = 0.;
-        for (int i = 0; i < 9; ++i) fro += hh[i] * hh[i];
-        bool ok = fabs(hh[8]) >= (double)GF_H_H22_FRAC * sqrt(fro);
-        float out[9];
-        for (int i = 0; i < 9; ++i) { out[i] = (float)(hh[i] / hh[8]); ok = ok && isfinite(out[i]); }
-        for (int i = 0; i < 9; ++i) Hn[i] = ok ? out[i] : (i % 4 == 0 ? 1.f : 0.f);
-        w.state[b * 4 + ST_REFIT_OK] = ok ? 1 : 0;
-    }
+    refit_solve(red, A, V, GF_H_JACOBI, t, m, part);
+    if (tid == 0) h_refit_tail(m, t, (double)GF_H_H22_FRAC, Hn, refit_ok);
 }
 
 __global__ __launch_bounds__(256) void h_rescore_kernel(Ws w, int M, float th2) {
     __shared__ int ired[4];
-    rescore_pair(w, blockIdx.x, M, [=]() { return th2; }, ired, Inlier());
+    rescore_pair(w, blockIdx.x, ired, TransferInlier(), point_part(w, blockIdx.x, M, th2));
 }
 
 // outputs.  ransac != 0: the current model, its flags scattered to the keypoints of view 0, its count; else the refit alone
@@ -247,7 +219,8 @@ __global__ __launch_bounds__(256) void h_final_kernel(Ws w, int M, int ransac, f
         success[b] = ok ? 1 : 0;
         if (num_inliers != nullptr) num_inliers[b] = (ok && ransac) ? w.state[b * 4 + ST_COUNT] : 0;
     }
-    if (inliers != nullptr) scatter_flags(w, b, M, ok, inliers);
+    if (inliers != nullptr)
+        scatter_flags(w.flags + (int64_t)b * M, w.idx + (int64_t)b * M, w.K[b], M, ok, inliers + (int64_t)b * M);
 }
 
 inline int check_common(const void* kp0, const void* kp1, const void* m0, int B, int M, int N, int T, const void* ws,

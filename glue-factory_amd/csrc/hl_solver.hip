@@ -10,7 +10,9 @@
 // A call is a fixed chain of kernels on one stream, 4 + 2 lo_iters launches (compact, score, select, lo_iters x (refit,
 // rescore), outputs), one workgroup of 256 lanes per pair except the scoring kernel (one workgroup per GF_HL_HYPS hypotheses
 // of a pair, one hypothesis per lane).  Kernel nodes only, nothing allocated, no host read: every kernel takes the pair's
-// counts K_p, K_l from the workspace.  The skeleton is ransac_common.h (its two-part templates); what is here is the model.
+// counts K_p, K_l from the workspace.  The skeleton is ransac_common.h, run over two parts (the points, then the lines); the
+// point side of the model (inlier rule, DLT rows, the tail of the refit) is h_model.h, shared with h_solver.hip; what is here
+// is the rest of the model: the fit's inputs, the line inlier rule and the line side of the refit.
 //
 // Compaction.  Point matches exactly as compact_pair orders them (ascending i, an index outside [0, N) is no match).  Line
 // match i is j = line_matches0[b, i] with 0 <= j < L1: the endpoints p, q of segment i of view 0 and r, s of segment j of
@@ -27,8 +29,8 @@
 // |(H x0) / w - x1|^2 < th^2.  A line match is an inlier when w(p) and w(q) are finite and > 0 and
 // max(|l . pi(H p)|, |l . pi(H q)|) < th  with l . (X, Y) = a X + b Y + c.  A hypothesis' score is the integer point inliers +
 // line inliers; the winner key and the tie rule (lowest index) are pack_key's.  Points stream through LDS in tiles of
-// GF_HL_TILE, then lines (endpoints and line, two tiles), all as broadcast reads.  The lane that holds its workgroup's best key
-// leaves its model in the workspace, so the select kernel fits nothing again.
+// GF_HL_TILE, then lines (endpoints and line side by side, a tile of twice the bytes), all as broadcast reads.  The lane that
+// holds its workgroup's best key leaves its model in the workspace, so the select kernel fits nothing again.
 //
 // Refit, fp64.  Hartley normalisation (centroid, mean distance sqrt 2) of view 0 over the flagged points and the endpoints
 // p, q of the flagged lines, of view 1 over the flagged points and the endpoints r, s of the flagged lines.  Two rows per
@@ -37,7 +39,7 @@
 // At least 4 flagged features.  The rescore replaces the current model only when the refit is valid and the total count
 // does not drop.
 #include "hl_fit.h"
-#include "ransac_common.h"
+#include "h_model.h"
 
 namespace {
 
@@ -63,24 +65,47 @@ inline size_t carve(void* base, int B, int M, int L, int T, Ws* w) {
     return c.off;
 }
 
-struct PointInlier {
-    __device__ __forceinline__ bool operator()(const float* h, float4 c, float th2) const {
-        const float w = h[6] * c.x + h[7] * c.y + h[8];
-        const float iw = 1.f / w;
-        const float dx = (h[0] * c.x + h[1] * c.y + h[2]) * iw - c.z;
-        const float dy = (h[3] * c.x + h[4] * c.y + h[5]) * iw - c.w;
-        return (w > 0.f) && isfinite(w) && (dx * dx + dy * dy < th2);      // a NaN error compares false
-    }
-};
-
-struct LineInlier {
-    __device__ __forceinline__ bool operator()(const float* h, float4 e, float4 l, float th) const {
+struct Inlier : TransferInlier {                                   // a point match by gf_h_ransac's rule
+    using TransferInlier::operator();
+    __device__ __forceinline__ bool operator()(const float* h, LineFeature f, float th) const {
+        const float4 e = f.e, l = f.l;
         const float w0 = h[6] * e.x + h[7] * e.y + h[8], w1 = h[6] * e.z + h[7] * e.w + h[8];
         const float i0 = 1.f / w0, i1 = 1.f / w1;
         const float d0 = l.x * ((h[0] * e.x + h[1] * e.y + h[2]) * i0) + l.y * ((h[3] * e.x + h[4] * e.y + h[5]) * i0) + l.z;
         const float d1 = l.x * ((h[0] * e.z + h[1] * e.w + h[2]) * i1) + l.y * ((h[3] * e.z + h[4] * e.w + h[5]) * i1) + l.z;
         // max(|d0|, |d1|) < th as two comparisons: a NaN distance compares false (fmaxf would drop it)
         return (w0 > 0.f) && (w1 > 0.f) && isfinite(w0) && isfinite(w1) && (fabsf(d0) < th) && (fabsf(d1) < th);
+    }
+};
+
+// the line part of the refit: the flagged line matches k < K; each has two points per view, the endpoints
+struct LineRefit {
+    const float4* seg;
+    const uint8_t* flags;
+    int K;
+    __device__ __forceinline__ bool keep(int k) const { return flags[k] != 0; }
+    __device__ __forceinline__ void moments(int k, double (&s)[6]) const {
+        const float4 e = seg[2 * k], g = seg[2 * k + 1];
+        s[0] += 1.; s[1] += 2.; s[2] += (double)e.x + e.z; s[3] += (double)e.y + e.w;
+        s[4] += (double)g.x + g.z; s[5] += (double)g.y + g.w;
+    }
+    __device__ __forceinline__ void spread(int k, const Hartley& t, double (&s)[2]) const {
+        auto dist = [](double x, double y, double cx, double cy) { return sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy)); };
+        const float4 e = seg[2 * k], g = seg[2 * k + 1];
+        s[0] += dist(e.x, e.y, t.cx0, t.cy0) + dist(e.z, e.w, t.cx0, t.cy0);
+        s[1] += dist(g.x, g.y, t.cx1, t.cy1) + dist(g.z, g.w, t.cx1, t.cy1);
+    }
+    // rows (a x, a y, a, b x, b y, b, c x, c y, c) at p' and q' with (a, b, c) the unit-normal line through r', s'
+    __device__ __forceinline__ void rows(int k, const Hartley& t, double (&acc)[45]) const {
+        const float4 e = seg[2 * k], g = seg[2 * k + 1];
+        const double x0 = (e.x - t.cx0) * t.sc0, y0 = (e.y - t.cy0) * t.sc0, x1 = (e.z - t.cx0) * t.sc0, y1 = (e.w - t.cy0) * t.sc0;
+        const double u0 = (g.x - t.cx1) * t.sc1, v0 = (g.y - t.cy1) * t.sc1, u1 = (g.z - t.cx1) * t.sc1, v1 = (g.w - t.cy1) * t.sc1;
+        const double la = v0 - v1, lb = u1 - u0, lc = u0 * v1 - u1 * v0;
+        const double inv = 1. / sqrt(la * la + lb * lb);
+        const double a = la * inv, bb = lb * inv, c = lc * inv;
+        const double r0[9] = {a * x0, a * y0, a, bb * x0, bb * y0, bb, c * x0, c * y0, c};
+        const double r1[9] = {a * x1, a * y1, a, bb * x1, bb * y1, bb, c * x1, c * y1, c};
+        add_rows<false>(acc, r0, r1);
     }
 };
 
@@ -97,8 +122,7 @@ __global__ __launch_bounds__(256) void hl_compact_kernel(const float* kp0, const
 // to the workspace
 __global__ __launch_bounds__(256) void hl_score_kernel(Ws w, int M, int L, int T, int nblk, float th, uint32_t seed,
                                                        int* samples, float* hyp_H, int* hyp_counts) {
-    __shared__ float4 tile[TILE];
-    __shared__ float4 tile_l[TILE];
+    __shared__ LineFeature tile[TILE];                            // the point pass uses the first half
     __shared__ unsigned long long red[4];
     const int b = blockIdx.x / nblk, blk = blockIdx.x % nblk, tid = threadIdx.x;
     const int t = blk * HYPS + tid;
@@ -144,8 +168,8 @@ __global__ __launch_bounds__(256) void hl_score_kernel(Ws w, int M, int L, int T
 #pragma unroll
         for (int i = 0; i < 9; ++i) hp[i] = h[i];
     }
-    const int np = tile_count<TILE>(h, corr, Kp, th * th, tile, PointInlier());
-    const int nl = tile_count_lines<TILE>(h, seg, line, Kl, th, tile, tile_l, LineInlier());
+    const int np = tile_count<TILE>(h, PointPart{corr, nullptr, Kp, th * th}, reinterpret_cast<float4*>(tile), Inlier());
+    const int nl = tile_count<TILE>(h, LinePart{seg, line, nullptr, Kl, th}, tile, Inlier());
     if (hyp_counts != nullptr && t < T) {
         hyp_counts[((int64_t)b * T + t) * 2] = ok ? np : -1;
         hyp_counts[((int64_t)b * T + t) * 2 + 1] = ok ? nl : -1;
@@ -173,7 +197,7 @@ __global__ __launch_bounds__(256) void hl_select_kernel(Ws w, int M, int L, int 
     float h[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) h[i] = ok ? hs[i] : 0.f;          // an all-zero model flags nothing
-    set_current2(w.p, w.l, b, M, L, h, hs, ok, th, ired, PointInlier(), LineInlier());
+    set_current(w.p, b, h, hs, ok, ired, Inlier(), point_part(w.p, b, M, th * th), line_part(w.l, b, L, th));
 }
 
 // Hartley-normalised DLT over the flagged points and lines of the current model -> refit, state[ST_REFIT_OK]
@@ -181,121 +205,29 @@ __global__ __launch_bounds__(256) void hl_refit_kernel(Ws w, int M, int L) {
     __shared__ double red[4 * 45];
     __shared__ double A[9][9], V[9][9];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float4* corr = w.p.corr + (int64_t)b * M;
-    const float4* seg = w.l.seg + 2 * (int64_t)b * L;
     const uint8_t* pf = w.p.flags + (int64_t)b * M;
-    const uint8_t* lf = w.l.flags + (int64_t)b * L;
     float* Hn = w.p.refit + (int64_t)b * 12;
+    int* refit_ok = w.p.state + b * 4 + ST_REFIT_OK;
     const bool have = w.p.state[b * 4 + ST_CUR_OK] != 0;            // nothing is kept where the pair has no current model
-    const int Kp = have ? w.p.K[b] : 0, Kl = have ? w.l.K[b] : 0;
-    // pass 1: the feature count, the point count (a line has two) and the centroids
-    double s6[6] = {0., 0., 0., 0., 0., 0.};
-    for (int k = tid; k < Kp; k += 256)
-        if (pf[k]) {
-            const float4 c = corr[k];
-            s6[0] += 1.; s6[1] += 1.; s6[2] += c.x; s6[3] += c.y; s6[4] += c.z; s6[5] += c.w;
-        }
-    for (int k = tid; k < Kl; k += 256)
-        if (lf[k]) {
-            const float4 e = seg[2 * k], g = seg[2 * k + 1];
-            s6[0] += 1.; s6[1] += 2.; s6[2] += (double)e.x + e.z; s6[3] += (double)e.y + e.w;
-            s6[4] += (double)g.x + g.z; s6[5] += (double)g.y + g.w;
-        }
-    block_sum_f64<6>(s6, red);
-    if (!(s6[0] >= 4.)) {                                           // uniform over the workgroup
-        if (tid < 9) Hn[tid] = (tid % 4 == 0) ? 1.f : 0.f;
-        if (tid == 0) w.p.state[b * 4 + ST_REFIT_OK] = 0;
+    const auto pts = point_refit(
+        w.p.corr + (int64_t)b * M, have ? w.p.K[b] : 0, [=](int k) { return pf[k] != 0; },
+        [](double (&acc)[45], int, double x, double y, double u, double v) { add_point_rows<false>(acc, x, y, u, v); });
+    const LineRefit lns{w.l.seg + 2 * (int64_t)b * L, w.l.flags + (int64_t)b * L, have ? w.l.K[b] : 0};
+    Hartley t;
+    refit_moments(red, t, pts, lns);
+    if (!(t.n >= 4.)) {                                             // uniform over the workgroup
+        h_refit_none(Hn, refit_ok);
         return;
     }
-    const double npts = s6[1], cx0 = s6[2] / npts, cy0 = s6[3] / npts, cx1 = s6[4] / npts, cy1 = s6[5] / npts;
-    // pass 2: mean distances to the centroids
-    double s2[2] = {0., 0.};
-    auto dist = [](double x, double y, double cx, double cy) { return sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy)); };
-    for (int k = tid; k < Kp; k += 256)
-        if (pf[k]) {
-            const float4 c = corr[k];
-            s2[0] += dist(c.x, c.y, cx0, cy0);
-            s2[1] += dist(c.z, c.w, cx1, cy1);
-        }
-    for (int k = tid; k < Kl; k += 256)
-        if (lf[k]) {
-            const float4 e = seg[2 * k], g = seg[2 * k + 1];
-            s2[0] += dist(e.x, e.y, cx0, cy0) + dist(e.z, e.w, cx0, cy0);
-            s2[1] += dist(g.x, g.y, cx1, cy1) + dist(g.z, g.w, cx1, cy1);
-        }
-    block_sum_f64<2>(s2, red);
-    const double sc0 = 1.4142135623730951 / (s2[0] / npts), sc1 = 1.4142135623730951 / (s2[1] / npts);
-    // pass 3: the 45 distinct sums of the normal matrix
-    double acc[45];
-#pragma unroll
-    for (int i = 0; i < 45; ++i) acc[i] = 0.;
-    auto add = [&](const double (&r0)[9], const double (&r1)[9]) {
-        int at = 0;
-#pragma unroll
-        for (int i = 0; i < 9; ++i)
-#pragma unroll
-            for (int j = i; j < 9; ++j) { acc[at] += r0[i] * r0[j] + r1[i] * r1[j]; ++at; }
-    };
-    for (int k = tid; k < Kp; k += 256)
-        if (pf[k]) {
-            const float4 c = corr[k];
-            const double x = (c.x - cx0) * sc0, y = (c.y - cy0) * sc0, u = (c.z - cx1) * sc1, v = (c.w - cy1) * sc1;
-            const double r0[9] = {0., 0., 0., -x, -y, -1., v * x, v * y, v};
-            const double r1[9] = {x, y, 1., 0., 0., 0., -u * x, -u * y, -u};
-            add(r0, r1);
-        }
-    for (int k = tid; k < Kl; k += 256)
-        if (lf[k]) {
-            const float4 e = seg[2 * k], g = seg[2 * k + 1];
-            const double x0 = (e.x - cx0) * sc0, y0 = (e.y - cy0) * sc0, x1 = (e.z - cx0) * sc0, y1 = (e.w - cy0) * sc0;
-            const double u0 = (g.x - cx1) * sc1, v0 = (g.y - cy1) * sc1, u1 = (g.z - cx1) * sc1, v1 = (g.w - cy1) * sc1;
-            const double la = v0 - v1, lb = u1 - u0, lc = u0 * v1 - u1 * v0;
-            const double inv = 1. / sqrt(la * la + lb * lb);
-            const double a = la * inv, bb = lb * inv, c = lc * inv;
-            const double r0[9] = {a * x0, a * y0, a, bb * x0, bb * y0, bb, c * x0, c * y0, c};
-            const double r1[9] = {a * x1, a * y1, a, bb * x1, bb * y1, bb, c * x1, c * y1, c};
-            add(r0, r1);
-        }
-    block_sum_f64<45>(acc, red);
-    __syncthreads();
-    if (tid == 0) {
-        int at = 0;
-        for (int i = 0; i < 9; ++i)
-            for (int j = i; j < 9; ++j) { A[i][j] = acc[at]; A[j][i] = acc[at]; ++at; }
-        for (int i = 0; i < 9; ++i)
-            for (int j = 0; j < 9; ++j) V[i][j] = i == j ? 1. : 0.;
-    }
-    __syncthreads();
-    gf_jacobi9(A, V, GF_HL_JACOBI, tid);
-    if (tid == 0) {
-        int best = 0;
-        for (int i = 1; i < 9; ++i)
-            if (A[i][i] < A[best][best]) best = i;
-        double g[9], m[9], hh[9];
-        for (int i = 0; i < 9; ++i) g[i] = V[i][best];
-        for (int r = 0; r < 3; ++r) {                               // m = G T0
-            m[3 * r + 0] = g[3 * r + 0] * sc0;
-            m[3 * r + 1] = g[3 * r + 1] * sc0;
-            m[3 * r + 2] = g[3 * r + 2] - sc0 * (g[3 * r + 0] * cx0 + g[3 * r + 1] * cy0);
-        }
-        for (int c = 0; c < 3; ++c) {                               // H = T1^-1 m
-            hh[0 + c] = m[0 + c] / sc1 + cx1 * m[6 + c];
-            hh[3 + c] = m[3 + c] / sc1 + cy1 * m[6 + c];
-            hh[6 + c] = m[6 + c];
-        }
-        double fro = 0.;
-        for (int i = 0; i < 9; ++i) fro += hh[i] * hh[i];
-        bool ok = fabs(hh[8]) >= (double)GF_HL_H22_FRAC * sqrt(fro);
-        float out[9];
-        for (int i = 0; i < 9; ++i) { out[i] = (float)(hh[i] / hh[8]); ok = ok && isfinite(out[i]); }
-        for (int i = 0; i < 9; ++i) Hn[i] = ok ? out[i] : (i % 4 == 0 ? 1.f : 0.f);
-        w.p.state[b * 4 + ST_REFIT_OK] = ok ? 1 : 0;
-    }
+    double m[9];
+    refit_solve(red, A, V, GF_HL_JACOBI, t, m, pts, lns);
+    if (tid == 0) h_refit_tail(m, t, (double)GF_HL_H22_FRAC, Hn, refit_ok);
 }
 
 __global__ __launch_bounds__(256) void hl_rescore_kernel(Ws w, int M, int L, float th) {
     __shared__ int ired[4];
-    rescore_pair2(w.p, w.l, blockIdx.x, M, L, th, ired, PointInlier(), LineInlier());
+    const int b = blockIdx.x;
+    rescore_pair(w.p, b, ired, Inlier(), point_part(w.p, b, M, th * th), line_part(w.l, b, L, th));
 }
 
 // outputs: the current model, its flags scattered to the keypoints and the segments of view 0, its counts
@@ -311,9 +243,10 @@ __global__ __launch_bounds__(256) void hl_final_kernel(Ws w, int M, int L, float
         num_inliers[2 * b] = ok ? total - nl : 0;
         num_inliers[2 * b + 1] = ok ? nl : 0;
     }
-    if (M > 0) scatter_flags(w.p, b, M, ok, inliers);
+    if (M > 0) scatter_flags(w.p.flags + (int64_t)b * M, w.p.idx + (int64_t)b * M, w.p.K[b], M, ok, inliers + (int64_t)b * M);
     __syncthreads();
-    if (L > 0) scatter_line_flags(w.l, b, L, ok, line_inliers);
+    if (L > 0)
+        scatter_flags(w.l.flags + (int64_t)b * L, w.l.idx + (int64_t)b * L, w.l.K[b], L, ok, line_inliers + (int64_t)b * L);
 }
 
 inline bool sizes_ok(int B, int M, int L, int T) {
@@ -338,10 +271,8 @@ extern "C" int gf_hl_ransac(const float* kpts0, const float* kpts1, const int64_
         return GF_ERR_SHAPE;
     if (ws == nullptr || H == nullptr || num_inliers == nullptr || success == nullptr) return GF_ERR_SHAPE;
     const int64_t nblk = nblk_of(T);
-    if ((int64_t)B * nblk >= ((int64_t)1 << 31) || (int64_t)B * T >= ((int64_t)1 << 31) || (int64_t)M + L >= ((int64_t)1 << 31))
-        return GF_ERR_UNSUPPORTED;
-    if (ws_bytes < (int64_t)carve(nullptr, B, M, L, T, nullptr)) return GF_ERR_SHAPE;
-    if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) return GF_ERR_ALIGN;
+    if ((int64_t)M + L >= ((int64_t)1 << 31)) return GF_ERR_UNSUPPORTED;
+    if (int e = ws_check(B, ws, ws_bytes, nblk, T, carve(nullptr, B, M, L, T, nullptr))) return e;
     if (!(ransac_th > 0.f) || !(ransac_th < 1e18f) || lo_iters < 0 || lo_iters > 64) return GF_ERR_SHAPE;
     Ws w;
     carve(ws, B, M, L, T, &w);

@@ -1,11 +1,12 @@
 """The shared yardstick's own test (no GPU): tests/ransac_cases.py restates the sampling of csrc/ransac_common.h for both
 solvers, so it is checked here for either sample size, with the mutation its users must catch.  Also the host view of the
-shared workspace: the byte counts of the two entries are the sums of their 16-byte aligned parts, whatever the order."""
+shared workspace: the byte counts of the three entries are the sums of their 16-byte aligned parts, whatever the order."""
 import numpy as np
 import pytest
 
 import e_solver_cases as ec
 import h_solver_cases as hc
+import hl_solver_cases as hl
 import ransac_cases as rc
 
 
@@ -27,11 +28,22 @@ def _al16(x):
     return (x + 15) & ~15
 
 
+def _core(B, M, nblk):
+    return sum(_al16(x) for x in (4 * B, 4 * B * M, 16 * B * M, 8 * B * nblk, 48 * B, 48 * B, 16 * B, B * M))
+
+
 @pytest.mark.parametrize("B,M,T", [(1, 1, 1), (2, 40, 10), (3, 257, 257), (1, 2048, 256), (32, 2048, 3000), (5, 1, 517)])
 def test_workspace_sizes_are_the_sums_of_their_aligned_parts(B, M, T):
     from glue_factory_amd import lib
     L = lib.load()
-    core = lambda nblk: sum(_al16(x) for x in (4 * B, 4 * B * M, 16 * B * M, 8 * B * nblk, 48 * B, 48 * B, 16 * B, B * M))
-    assert L.gf_h_ws_bytes(B, M, T) == core((T + hc.HYPS - 1) // hc.HYPS)
+    assert L.gf_h_ws_bytes(B, M, T) == _core(B, M, (T + hc.HYPS - 1) // hc.HYPS)
     extra = _al16(4 * 9 * ec.MAXSOL * B * T) + _al16(4 * B * T)
-    assert L.gf_e_ws_bytes(B, M, T) == core((T * ec.MAXSOL + ec.HYPS - 1) // ec.HYPS) + extra
+    assert L.gf_e_ws_bytes(B, M, T) == _core(B, M, (T * ec.MAXSOL + ec.HYPS - 1) // ec.HYPS) + extra
+
+
+@pytest.mark.parametrize("B,M,Ln,T", [(1, 1, 0, 1), (1, 0, 1, 1), (2, 40, 7, 10), (3, 257, 257, 257)])
+def test_point_and_line_workspace_size_is_the_core_the_line_part_and_the_block_models(B, M, Ln, T):
+    from glue_factory_amd import lib
+    nblk = (T + hl.HYPS - 1) // hl.HYPS
+    lines = sum(_al16(x) for x in (4 * B, 4 * B * Ln, 2 * 16 * B * Ln, 16 * B * Ln, B * Ln))
+    assert lib.load().gf_hl_ws_bytes(B, M, Ln, T) == _core(B, M, nblk) + lines + _al16(4 * 12 * B * nblk)
