@@ -244,31 +244,67 @@ __global__ __launch_bounds__(512, 2) void gemm_st_kernel(GsParams p) {
     gs_wait_vm<0>();                                              // the re-fetched tail tiles and the last stores
 }
 
+// Geometry of one streamed launch over M rows, N channels at K = K0 + K1: the ONLY place that decides it (gs_launch and,
+// through gf_gemm_stream_plan, gf_gemm_plan both ask here).  Workgroup x of channel group y owns the tiles x, x + gx, ...
+struct GsGrid { int tr, gx, gy, tmin, tmax; };     // rows per tile, grid, fewest / most tiles of a workgroup
+GsGrid gs_grid(int M, int N, int K) {
+    GsGrid g;
+    g.tr = GS_TILE / (2 * K);
+    const int ntile = M / g.tr;
+    g.gy = N / 256;
+    g.gx = GS_WGS / g.gy;                                     // one workgroup per CU over all channel groups
+    if (g.gx < 1) g.gx = 1;
+    if (g.gx > ntile) g.gx = ntile;
+    g.tmin = ntile / g.gx;
+    g.tmax = (ntile + g.gx - 1) / g.gx;
+    return g;
+}
+
+// Which calls the streamed kernel serves (bf16 only: the caller checks the dtype)
+bool gs_serves(int M, int N, int K0, int K1, bool cs, int rot_n, bool res, bool res2) {
+    const int K = K0 + K1;
+    if ((K != 256 && K != 512) || N % 256 || M % 64 || (K1 && K1 != K0)) return false;
+    if (cs && (rot_n % 256 || rot_n <= 0 || rot_n > N || res || K1)) return false;
+    if (res2 && (!res || cs)) return false;
+    return true;
+}
+
 template <int KF, bool TWO, int RES, bool ROT = false>
 int gs_launch(const GsParams& p, hipStream_t st) {
-    constexpr int TR = GS_TILE / (32 * KF);
     const size_t lds = (size_t)GS_NSTAGE * GS_TILE;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_st_kernel<KF, TWO, RES, ROT>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    const int ntile = p.M / TR, ncg = p.N / 256;
-    int gx = GS_WGS / ncg;                                    // one workgroup per CU over all channel groups
-    if (gx < 1) gx = 1;
-    if (gx > ntile) gx = ntile;
-    gemm_st_kernel<KF, TWO, RES, ROT><<<dim3(gx, ncg), dim3(512), lds, st>>>(p);
+    const GsGrid g = gs_grid(p.M, p.N, 16 * KF);
+    gemm_st_kernel<KF, TWO, RES, ROT><<<dim3(g.gx, g.gy), dim3(512), lds, st>>>(p);
     return (int)hipGetLastError();
 }
 
 }  // namespace
+
+// Internal (not part of the C ABI), host only: the launches gf_gemm_stream_try would make for this call -- 0 when it answers
+// GF_ERR_UNSUPPORTED, else their number (2: a rotary launch over rot_n channels, then a plain one over the rest) with
+// out[5 l ..] = {grid x, grid y, rows per tile, fewest, most tiles of a workgroup} of launch l.
+int gf_gemm_stream_plan(int M, int N, int K0, int K1, bool cs, int rot_n, bool res, bool res2, int64_t* out) {
+    if (!gs_serves(M, N, K0, K1, cs, rot_n, res, res2)) return 0;
+    const int widths[2] = {cs ? rot_n : N, cs ? N - rot_n : 0};
+    int n = 0;
+    for (int l = 0; l < 2; ++l) {
+        if (widths[l] <= 0) continue;
+        const GsGrid g = gs_grid(M, widths[l], K0 + K1);
+        const int64_t v[5] = {g.gx, g.gy, g.tr, g.tmin, g.tmax};
+        for (int i = 0; i < 5; ++i) out[5 * n + i] = v[i];
+        ++n;
+    }
+    return n;
+}
 
 // Internal (not part of the C ABI): called by gf_gemm first; GF_ERR_UNSUPPORTED = "use the register-resident kernel".
 int gf_gemm_stream_try(const void* x0, const void* x1, const void* w, const float* bias, const void* res, void* y,
                        const float* cs, int rot_n, int M, int N, int K0, int K1, int64_t ld0, int64_t ld1, int64_t ldw,
                        int64_t ldr, int64_t ldy, hipStream_t st, const void* res2, int64_t ldr2) {
     const int K = K0 + K1;
-    if ((K != 256 && K != 512) || N % 256 || M % 64 || (K1 && K1 != K0)) return GF_ERR_UNSUPPORTED;
-    if (cs && (rot_n % 256 || rot_n <= 0 || rot_n > N || res || K1)) return GF_ERR_UNSUPPORTED;
-    if (res2 && (!res || cs)) return GF_ERR_UNSUPPORTED;
+    if (!gs_serves(M, N, K0, K1, cs != nullptr, rot_n, res != nullptr, res2 != nullptr)) return GF_ERR_UNSUPPORTED;
     GsParams p;
     p.x0 = static_cast<const bf16_t*>(x0); p.x1 = static_cast<const bf16_t*>(x1); p.w = static_cast<const bf16_t*>(w);
     p.bias = bias; p.res = static_cast<const bf16_t*>(res); p.res2 = static_cast<const bf16_t*>(res2);

@@ -328,39 +328,81 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_ws_kernel(GwParams p) {
     }
 }
 
-template <typename T, int KF, int R, bool TWO, int NW> int gw_launch(const GwParams& p, hipStream_t st) {
+// The instance that serves K in element size `es` (R 32-row blocks per wave, NW waves per workgroup; R = 0: none) and the
+// geometry of its launch: the ONLY place that decides either (gw_dispatch / gw_launch and gf_gemm_plan all ask here).
+// registers: x fragments = R * K/16 * (4 | 8) VGPRs, kept <= 128
+struct GwShape { int R, NW; };
+constexpr GwShape gw_shape(int es, int K) {
+    if (es == 2) {
+        switch (K) {
+            case 32: case 64: case 128: return {2, 4};
+            case 256: return {GW_R256, GW_NW256};
+            case 512: return {1, 8};                        // 32 KB slices: one 8-wave group per CU
+        }
+    } else {
+        switch (K) {
+            case 32: case 64: return {2, 4};
+            case 128: return {1, 4};
+            case 256: return {1, 8};
+        }
+    }
+    return {0, 0};
+}
+struct GwGrid { int rows, grid, bmin, bmax; };              // rows per workgroup block, grid, fewest / most blocks of a workgroup
+GwGrid gw_grid(int M, GwShape s) {
+    GwGrid g;
+    g.rows = s.NW * 32 * s.R;
+    const int nblk = (M + g.rows - 1) / g.rows;
+    g.grid = nblk;
+    if (GW_GRID > 0 && g.grid > GW_GRID) g.grid = GW_GRID;  // persistent: each workgroup walks row blocks b, b + grid, ...
+    g.bmin = nblk / g.grid;
+    g.bmax = (nblk + g.grid - 1) / g.grid;
+    return g;
+}
+
+template <typename T, int KF, bool TWO> int gw_launch(const GwParams& p, hipStream_t st) {
+    constexpr GwShape S = gw_shape((int)sizeof(T), 16 * KF);
     constexpr int ROWB = 16 * KF * (int)sizeof(T);
-    const size_t lds = 2 * (size_t)(ROWB * 32 > 16384 ? ROWB * 32 : 16384) + NW * GW_SCRATCH + (size_t)p.N * 4;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ws_kernel<T, KF, R, TWO, NW>),
+    const size_t lds = 2 * (size_t)(ROWB * 32 > 16384 ? ROWB * 32 : 16384) + S.NW * GW_SCRATCH + (size_t)p.N * 4;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ws_kernel<T, KF, S.R, TWO, S.NW>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    const int rows_per_wg = NW * 32 * R;
-    int grid = (p.M + rows_per_wg - 1) / rows_per_wg;
-    if (GW_GRID > 0 && grid > GW_GRID) grid = GW_GRID;      // persistent: each workgroup walks row blocks b, b + grid, ...
-    gemm_ws_kernel<T, KF, R, TWO, NW><<<dim3(grid), 64 * NW, lds, st>>>(p);
+    const GwGrid g = gw_grid(p.M, S);
+    gemm_ws_kernel<T, KF, S.R, TWO, S.NW><<<dim3(g.grid), 64 * S.NW, lds, st>>>(p);
     return (int)hipGetLastError();
 }
 
 template <typename T, bool TWO> int gw_dispatch(const GwParams& p, int K, hipStream_t st) {
-    // registers: x fragments = R * K/16 * (4 | 8) VGPRs, kept <= 128
-    if constexpr (sizeof(T) == 2) {
-        switch (K) {
-            case 32: return gw_launch<T, 2, 2, TWO, 4>(p, st);
-            case 64: return gw_launch<T, 4, 2, TWO, 4>(p, st);
-            case 128: return gw_launch<T, 8, 2, TWO, 4>(p, st);
-            case 256: return gw_launch<T, 16, GW_R256, TWO, GW_NW256>(p, st);
-            case 512: return gw_launch<T, 32, 1, TWO, 8>(p, st);     // 32 KB slices: one 8-wave group per CU
-        }
-    } else {
-        switch (K) {
-            case 32: return gw_launch<T, 2, 2, TWO, 4>(p, st);
-            case 64: return gw_launch<T, 4, 2, TWO, 4>(p, st);
-            case 128: return gw_launch<T, 8, 1, TWO, 4>(p, st);
-            case 256: return gw_launch<T, 16, 1, TWO, 8>(p, st);
-        }
+    switch (K) {
+        case 32: return gw_launch<T, 2, TWO>(p, st);
+        case 64: return gw_launch<T, 4, TWO>(p, st);
+        case 128: return gw_launch<T, 8, TWO>(p, st);
+        case 256: return gw_launch<T, 16, TWO>(p, st);
+        case 512: if constexpr (sizeof(T) == 2) return gw_launch<T, 32, TWO>(p, st);
     }
     return GF_ERR_UNSUPPORTED;
 }
+
+// the argument checks that gf_gemm and gf_gemm_plan share (pointers and row strides are gf_gemm's own)
+int gw_check(int M, int N, int K0, int K1, int dtype) {
+    if (M <= 0 || N <= 0 || K0 <= 0 || K1 < 0) return GF_ERR_SHAPE;
+    if (dtype != GF_BF16 && dtype != GF_F32) return GF_ERR_DTYPE;
+    if (N % 32 || (K1 && K1 != K0)) return GF_ERR_UNSUPPORTED;   // K in {32..512} checked by the dispatch
+    return 0;
+}
+int gw_check_rot(bool cs, int rot_n, int N) { return cs && (rot_n % 64 || rot_n > N) ? GF_ERR_SHAPE : 0; }
+// ... and those that gf_gemm_res2 and gf_gemm_plan share (the shapes themselves are gf_gemm_stream_try's to refuse)
+int gw_check_res2(int M, int N, int K0, int K1, int dtype, bool res, bool res_b) {
+    if (M <= 0 || N <= 0 || K0 <= 0 || K1 < 0) return GF_ERR_SHAPE;
+    if (dtype != GF_BF16 || !res || !res_b) return GF_ERR_UNSUPPORTED;
+    return 0;
+}
+// does gf_gemm ask the streamed kernel first?  (gf_gemm_res2 has no other kernel and always does)
+#ifndef GW_NO_STREAM
+constexpr bool GW_STREAM = true;
+#else
+constexpr bool GW_STREAM = false;
+#endif
 
 }  // namespace
 
@@ -374,6 +416,38 @@ extern "C" int gf_gemm_trace(unsigned long long* host, int n) {
 int gf_gemm_stream_try(const void* x0, const void* x1, const void* w, const float* bias, const void* res, void* y,
                        const float* cs, int rot_n, int M, int N, int K0, int K1, int64_t ld0, int64_t ld1, int64_t ldw,
                        int64_t ldr, int64_t ldy, hipStream_t st, const void* res2 = nullptr, int64_t ldr2 = 0);
+int gf_gemm_stream_plan(int M, int N, int K0, int K1, bool cs, int rot_n, bool res, bool res2, int64_t* out);
+
+// Host-only (no device needed): which kernel serves gf_gemm (has_res_b = 0) / gf_gemm_res2 (has_res_b = 1) for this call
+// and how it is distributed.  Returns 1 = streamed (gemm_st.hip), 0 = register-resident (this file), or the error code the
+// entry itself answers for these arguments (pointers and row strides aside).  out[11] = {launches, then per launch: grid x,
+// grid y, rows per tile (streamed) or per workgroup block (register-resident), fewest, most tiles / blocks of a workgroup};
+// the streamed rotary epilogue with rot_n < N is two launches (rot_n channels rotated, then the rest), all else one.
+extern "C" int gf_gemm_plan(int M, int N, int K0, int K1, int has_res, int has_res_b, int has_cs, int rot_n, int dtype,
+                            int64_t* out) {
+    if (out == nullptr) return GF_ERR_SHAPE;
+    for (int i = 0; i < 11; ++i) out[i] = 0;
+    if (has_res_b) {                                         // gf_gemm_res2 (it has no table argument)
+        if (const int e = gw_check_res2(M, N, K0, K1, dtype, has_res != 0, true)) return e;
+        if (has_cs) return GF_ERR_UNSUPPORTED;
+    } else {
+        if (const int e = gw_check(M, N, K0, K1, dtype)) return e;
+        if (const int e = gw_check_rot(has_cs != 0, rot_n, N)) return e;
+    }
+    if (dtype == GF_BF16 && (has_res_b || GW_STREAM)) {
+        if (const int n = gf_gemm_stream_plan(M, N, K0, K1, has_cs != 0, rot_n, has_res != 0, has_res_b != 0, out + 1)) {
+            out[0] = n;
+            return 1;
+        }
+    }
+    if (has_res_b) return GF_ERR_UNSUPPORTED;
+    const GwShape s = gw_shape(dtype == GF_BF16 ? 2 : 4, K0 + K1);
+    if (s.R == 0) return GF_ERR_UNSUPPORTED;
+    const GwGrid g = gw_grid(M, s);
+    const int64_t v[6] = {1, g.grid, 1, g.rows, g.bmin, g.bmax};
+    for (int i = 0; i < 6; ++i) out[i] = v[i];
+    return 0;
+}
 
 // y = [x0 | x1] W^T + bias + res + res_b: gf_gemm with TWO residual inputs, streamed-activation kernel only (bf16,
 // K0 + K1 in {256, 512}, N % 256 == 0, M % 64 == 0, no rotary epilogue; GF_ERR_UNSUPPORTED otherwise: add one of the
@@ -381,8 +455,8 @@ int gf_gemm_stream_try(const void* x0, const void* x1, const void* w, const floa
 extern "C" int gf_gemm_res2(const void* x0, const void* x1, const void* w, const float* bias, const void* res, const void* res_b,
                             void* y, int M, int N, int K0, int K1, int64_t ld0, int64_t ld1, int64_t ldw, int64_t ldr,
                             int64_t ldr_b, int64_t ldy, int dtype, void* stream) {
-    if (M <= 0 || N <= 0 || K0 <= 0 || K1 < 0) return GF_ERR_SHAPE;
-    if (dtype != GF_BF16 || !res || !res_b || (K1 && !x1)) return GF_ERR_UNSUPPORTED;
+    if (const int e = gw_check_res2(M, N, K0, K1, dtype, res != nullptr, res_b != nullptr)) return e;
+    if (K1 && !x1) return GF_ERR_UNSUPPORTED;
     if (ld0 % 8 || (K1 && ld1 % 8) || ldw % 8 || ldy % 8 || ldr % 8 || ldr_b % 8) return GF_ERR_ALIGN;
     return gf_gemm_stream_try(x0, x1, w, bias, res, y, nullptr, 0, M, N, K0, K1, ld0, ld1, ldw, ldr, ldy,
                               reinterpret_cast<hipStream_t>(stream), res_b, ldr_b);
@@ -391,23 +465,20 @@ extern "C" int gf_gemm_res2(const void* x0, const void* x1, const void* w, const
 extern "C" int gf_gemm(const void* x0, const void* x1, const void* w, const float* bias, const void* res, void* y,
                        const float* cs, int rot_n, int M, int N, int K0, int K1,
                        int64_t ld0, int64_t ld1, int64_t ldw, int64_t ldr, int64_t ldy, int dtype, void* stream) {
-    if (M <= 0 || N <= 0 || K0 <= 0 || K1 < 0) return GF_ERR_SHAPE;
-    if (dtype != GF_BF16 && dtype != GF_F32) return GF_ERR_DTYPE;
+    if (const int e = gw_check(M, N, K0, K1, dtype)) return e;
     const int K = K0 + K1;
-    if (N % 32 || (K1 && K1 != K0) || (K1 && !x1)) return GF_ERR_UNSUPPORTED;   // K in {32..512} checked by the dispatch
+    if (K1 && !x1) return GF_ERR_UNSUPPORTED;
     const int al = dtype == GF_BF16 ? 8 : 4;                // 16-byte aligned rows of x / W / y / res
     if (ld0 % al || (K1 && ld1 % al) || ldw % al || ldy % al || (res && ldr % al)) return GF_ERR_ALIGN;
-    if (cs && (rot_n % 64 || rot_n > N)) return GF_ERR_SHAPE;
+    if (const int e = gw_check_rot(cs != nullptr, rot_n, N)) return e;
     GwParams p;
     p.x0 = x0; p.x1 = x1; p.w = w; p.bias = bias; p.res = res; p.y = y; p.cs = cs; p.rot_n = cs ? rot_n : 0;
     p.M = M; p.N = N; p.K0 = K0; p.K1 = K1; p.ld0 = ld0; p.ld1 = ld1; p.ldw = ldw; p.ldr = ldr; p.ldy = ldy;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#ifndef GW_NO_STREAM
-    if (dtype == GF_BF16) {
+    if (GW_STREAM && dtype == GF_BF16) {
         const int e = gf_gemm_stream_try(x0, x1, w, bias, res, y, cs, rot_n, M, N, K0, K1, ld0, ld1, ldw, ldr, ldy, st);
         if (e != GF_ERR_UNSUPPORTED) return e;
     }
-#endif
     if (dtype == GF_BF16) return K1 ? gw_dispatch<bf16_t, true>(p, K, st) : gw_dispatch<bf16_t, false>(p, K, st);
     return K1 ? gw_dispatch<float, true>(p, K, st) : gw_dispatch<float, false>(p, K, st);
 }

@@ -363,6 +363,14 @@ int gf_gemm_res2(const void* x0, const void* x1, const void* w, const float* bia
                  void* y, int M, int N, int K0, int K1, int64_t ld0, int64_t ld1, int64_t ldw, int64_t ldr,
                  int64_t ldr_b, int64_t ldy, int dtype, void* stream);
 
+/* gf_gemm_plan: host-only query (no device needed): which kernel serves gf_gemm (has_res_b = 0) or gf_gemm_res2 (has_res_b = 1)
+ * for this call, and how its launches are distributed -- computed by the functions the launches themselves ask.  Returns
+ * 1 = streamed-activation kernel (csrc/gemm_st.hip), 0 = register-resident kernel (csrc/gemm_ws.hip), or the GF_ERR_* code the
+ * entry answers for these arguments (pointers and row strides aside).  out[11] = {launches, then for each launch: grid x,
+ * grid y, rows per tile (streamed) or per workgroup block (register-resident), fewest, most tiles / blocks that one workgroup
+ * walks}; a streamed rotary call with rot_n < N is two launches (rot_n rotated channels, then the rest), every other call one. */
+int gf_gemm_plan(int M, int N, int K0, int K1, int has_res, int has_res_b, int has_cs, int rot_n, int dtype, int64_t* out);
+
 /* ---- weight / bias gradient of a linear layer (autograd of every nn.Linear on the path,
  * lightglue.py:131-221, 271-290): dW[n][k] = sum_m dY[m][n] X[m][k], db[n] = sum_m dY[m][n]
  * with dY [M,Nout], X [M,K] row-major in `dtype` and fp32 outputs dW [Nout,K], db [Nout]
