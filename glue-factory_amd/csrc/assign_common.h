@@ -3,7 +3,7 @@
 // through LDS in 64-row tiles; the tile is computed as C[tile_row][owner], so every reduction over the streamed axis is
 // lane-local (see gf_common.h and the header of assignment.hip).
 #pragma once
-#include "gf_common.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -137,9 +137,7 @@ template <typename T, int D> size_t head_lds() { return 2 * ALay<T, D>::TILE * s
 
 template <typename K> int set_lds(K kern, size_t bytes) {
     if (bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return (int)e;
+        if (int e = gf_allow_lds(kern, bytes)) return e;
     }
     return 0;
 }

@@ -15,6 +15,7 @@
 // lane-local (see gf_common.h).  Kernels that write N x N data make the owner the CONTIGUOUS
 // (column) index of the output so a half-wave writes 32 consecutive elements of one row.
 #include <cstdlib>
+#include "gf_launch.h"
 #include "gf_common.h"
 #include "assign_common.h"
 #include "gf_amd.h"
@@ -353,7 +354,7 @@ template <typename T, int D> int launch_td(int which, const HeadParams& p, hipSt
     {                                                               \
         if (int e = set_lds(kern<T, D>, lds)) return e;             \
         kern<T, D><<<dim3(total), dim3(256), lds, st>>>(p);         \
-        return (int)hipGetLastError();                              \
+        return gf_launched();                                       \
     }
     switch (which) {
         case K_LSE:
@@ -364,7 +365,7 @@ template <typename T, int D> int launch_td(int which, const HeadParams& p, hipSt
                 if (int e = set_lds(rows_lse_kernel<T, D, false>, lds)) return e;
                 rows_lse_kernel<T, D, false><<<dim3(total), dim3(256), lds, st>>>(p);
             }
-            return (int)hipGetLastError();
+            return gf_launched();
         case K_ARGMAX: GF_LAUNCH(rows_argmax_kernel)
         case K_WRITE: GF_LAUNCH(assign_write_kernel)
         case K_BWD: GF_LAUNCH(dual_softmax_bwd_kernel)
@@ -375,7 +376,7 @@ template <typename T, int D> int launch_td(int which, const HeadParams& p, hipSt
     {                                                                                 \
         if (int e = set_lds(rows_lse_argmax_kernel<T, D, flag>, lds)) return e;       \
         rows_lse_argmax_kernel<T, D, flag><<<dim3(total), dim3(256), lds, st>>>(p);   \
-        return (int)hipGetLastError();                                                \
+        return gf_launched();                                                         \
     }
     if (which == K_LSEARG) GF_LAUNCH2(true)
     GF_LAUNCH2(false)
@@ -401,10 +402,7 @@ int rejected(const HeadParams& p, int D, int dtype) {
 
 int launch(int which, const HeadParams& p, int D, int dtype, void* stream) {
     if (p.B <= 0 || p.No <= 0 || p.Ns <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_F32) return launch_t<float>(which, p, D, st);
-    if (dtype == GF_BF16) return launch_t<bf16_t>(which, p, D, st);
-    return GF_ERR_DTYPE;
+    return gf_by_dtype(dtype, [&](auto t) { return launch_t<decltype(t)>(which, p, D, gf_stream(stream)); });
 }
 
 }  // namespace
@@ -445,7 +443,7 @@ extern "C" int gf_assign_write(const void* a, const void* b, const float* rowbia
     p.nsplit = GF_WRITE_SPLIT;
     if (int e = rejected(p, D, dtype)) return e;      // a rejected call leaves expsum as it was
     if (expsum)
-        if (hipError_t e = gf_zero_f32(expsum, (size_t)B, reinterpret_cast<hipStream_t>(stream))) return (int)e;
+        if (hipError_t e = gf_zero_f32(expsum, (size_t)B, gf_stream(stream))) return (int)e;
     return launch(K_WRITE, p, D, dtype, stream);
 }
 
@@ -466,7 +464,7 @@ extern "C" int gf_filter_matches(const float* max0, const int64_t* arg0, const i
     if (B <= 0 || M <= 0 || N <= 0) return GF_ERR_SHAPE;
     int64_t tot = (int64_t)B * (M + N);
     int blocks = (int)((tot + 255) / 256);
-    filter_matches_kernel<<<dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    filter_matches_kernel<<<dim3(blocks), dim3(256), 0, gf_stream(stream)>>>(
         max0, arg0, arg1, th, m0, m1, s0, s1, B, M, N);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

@@ -8,8 +8,7 @@
 //
 // Layout: q,k,v,o are [B, N, H, hd] views with arbitrary element strides for (b, n, h) and
 // hd contiguous (so the fused Wqkv output is consumed in place).  lse/delta are [B,H,N] fp32.
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 #include "attn_common.h"
 
 using namespace gfattn;
@@ -30,7 +29,7 @@ int attn_params(AttnParams& p, const void* q, const void* k, const void* v, cons
     // the split products exist in the LDS-DMA bf16 kernels only (rows addressed through 32-bit buffer offsets)
     if ((flags & GF_ATTN_SPLIT) && !(kvdma_ok(Nk, ks[1]) && kvdma_ok(Nk, vs[1]))) return GF_ERR_UNSUPPORTED;
     if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0) return GF_ERR_SHAPE;
-    const int align = dtype == GF_BF16 ? 8 : 4;
+    const int align = gf_vec_elems(dtype);
     if (bad_stride(qs, align) || bad_stride(ks, align) || bad_stride(vs, align) ||
         bad_stride(os, (o_f32_if_split && (flags & GF_ATTN_SPLIT)) ? 4 : align))
         return GF_ERR_ALIGN;
@@ -81,7 +80,7 @@ extern "C" int gf_attn_fwd_ex(const void* q, const void* k, const void* v, void*
                             flags, GF_ATTN_SPLIT, false))
         return e;
     p.o32 = (p.flags & GF_ATTN_SPLIT) ? o32 : nullptr;
-    return launch_fwd(p, reinterpret_cast<hipStream_t>(stream), dtype, D);
+    return launch_fwd(p, gf_stream(stream), dtype, D);
 }
 
 extern "C" int gf_attn_bwd(const void* q, const void* k, const void* v, const void* o,
@@ -110,7 +109,7 @@ extern "C" int gf_attn_bwd_acc(const void* q, const void* k, const void* v, cons
     if (int e = attn_params(p, q, k, v, o, lse, B, H, Nq, Nk, D, q_strides, k_strides, v_strides, o_strides, scale, dtype,
                             flags, GF_ATTN_ACC_DQ | GF_ATTN_ACC_DK | GF_ATTN_SPLIT, true))
         return e;
-    const int align = dtype == GF_BF16 ? 8 : 4;
+    const int align = gf_vec_elems(dtype);
     if (bad_stride(do_strides, align) || bad_stride(dq_strides, align) || bad_stride(dk_strides, align) || bad_stride(dv_strides, align))
         return GF_ERR_ALIGN;
     p.dout = dout; p.delta = delta; p.dq = dq; p.dk = dk; p.dv = dv;
@@ -118,5 +117,5 @@ extern "C" int gf_attn_bwd_acc(const void* q, const void* k, const void* v, cons
     p.sdqb = dq_strides[0]; p.sdqn = dq_strides[1]; p.sdqh = dq_strides[2];
     p.sdkb = dk_strides[0]; p.sdkn = dk_strides[1]; p.sdkh = dk_strides[2];
     p.sdvb = dv_strides[0]; p.sdvn = dv_strides[1]; p.sdvh = dv_strides[2];
-    return launch_bwd(p, reinterpret_cast<hipStream_t>(stream), dtype, D);
+    return launch_bwd(p, gf_stream(stream), dtype, D);
 }

@@ -186,13 +186,12 @@ int launch_dq3_bf16(const AttnParams& p, hipStream_t st) {
     (void)hipGetDevice(&dev);
     if (dev >= 64 || !((attr_set >> dev) & 1ull)) {
         for (auto k : kern) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
+            if (int e = gf_allow_lds(k, lds)) return e;
         }
         if (dev < 64) attr_set |= 1ull << dev;
     }
     kern[((p.flags & GF_ATTN_SPLIT) ? 4 : 0) + (p.rr == 1.f ? 2 : 0) + (p.Nk % 64 == 0 ? 1 : 0)]<<<dim3(total), dim3(256), lds, st>>>(p);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 }  // namespace gfattn

@@ -293,7 +293,7 @@ int launch_dkv_bf16(const AttnParams& p, hipStream_t st) {
         if (dev < 64) attr_set |= 1ull << dev;
     }
     kern[((p.flags & GF_ATTN_SPLIT) ? 4 : 0) + (p.rr == 1.f ? 2 : 0) + (p.Nq % 64 == 0 ? 1 : 0)]<<<dim3(total), dim3(64 * NW), lds, st>>>(p);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 }  // namespace gfattn

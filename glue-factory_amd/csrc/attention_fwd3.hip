@@ -321,8 +321,7 @@ int launch_fwd3_bf16(const AttnParams& p, hipStream_t st) {
     (void)hipGetDevice(&dev);
     if (dev >= 64 || !((attr_set >> dev) & 1ull)) {
         for (auto k : kern) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
+            if (int e = gf_allow_lds(k, lds)) return e;
         }
         if (dev < 64) attr_set |= 1ull << dev;
     }
@@ -333,7 +332,7 @@ int launch_fwd3_bf16(const AttnParams& p, hipStream_t st) {
 #endif
     const bool split = (p.flags & GF_ATTN_SPLIT) != 0;
     kern[(split ? 4 : 0) + (pre ? 2 : 0) + (even ? 1 : 0)]<<<dim3(total), dim3(256), lds, st>>>(p);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 }  // namespace gfattn

@@ -589,14 +589,14 @@ template <typename T, int HD> int fwd(const AttnParams& p, hipStream_t st) {
     if (lds > ATTN_LDS_MAX) return GF_ERR_UNSUPPORTED;
     if (int e = set_lds(attn_fwd_kernel<T, HD>, lds)) return e;
     attn_fwd_kernel<T, HD><<<dim3(((p.Nq + 255) / 256) * p.H * p.B), dim3(256), lds, st>>>(p);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 template <typename T, int HD> int dq(const AttnParams& p, hipStream_t st) {
     const size_t lds = dq_lds<T, HD>();
     if (lds > ATTN_LDS_MAX) return GF_ERR_UNSUPPORTED;
     if (int e = set_lds(attn_bwd_dq_kernel<T, HD>, lds)) return e;
     attn_bwd_dq_kernel<T, HD><<<dim3(((p.Nq + 255) / 256) * p.H * p.B), dim3(256), lds, st>>>(p);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 template <typename T, int HD> int bwd(const AttnParams& p_, hipStream_t st) {
     if constexpr (sizeof(T) == 2 && HD == 64) {
@@ -609,21 +609,18 @@ template <typename T, int HD> int bwd(const AttnParams& p_, hipStream_t st) {
         if (int e = dq<T, HD>(p, st)) return e;
         if (int e = set_lds(attn_bwd_dkv_kernel<T, HD>, lds)) return e;
         attn_bwd_dkv_kernel<T, HD><<<dim3(((p.Nk + 127) / 128) * p.H * p.B), dim3(256), lds, st>>>(p);
-        return (int)hipGetLastError();
+        return gf_launched();
     }
 }
 
 // f(element type, head_dim) for the run-time dtype and D
 template <typename F> int by_type_and_dim(int dtype, int D, F f) {
-    auto by_dim = [&](auto t) {
+    return gf_by_dtype(dtype, [&](auto t) {
         if (D == 32) return f(t, std::integral_constant<int, 32>());
         if (D == 64) return f(t, std::integral_constant<int, 64>());
         if (D == 128) return f(t, std::integral_constant<int, 128>());
         return (int)GF_ERR_UNSUPPORTED;
-    };
-    if (dtype == GF_F32) return by_dim(float());
-    if (dtype == GF_BF16) return by_dim(bf16_t());
-    return (int)GF_ERR_DTYPE;
+    });
 }
 
 }  // namespace

@@ -20,8 +20,7 @@
 // per SIMD, up to 512 unified registers); streamed tiles of 64 tokens x {qk, dO, v} + statistics arrive by
 // `global_load ... lds` in a 3-stage ring (attn_common.h: chunk swizzle, ds_read_b128 row reads, ds_read_b64_tr_b16
 // transposed reads).
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 #include "attn_common.h"
 
 namespace gfattn {
@@ -332,7 +331,7 @@ extern "C" int gf_attn_cross_bwd(const void* qk, const void* v, const void* o, c
     p.sdvb = dv_strides[0]; p.sdvn = dv_strides[1]; p.sdvh = dv_strides[2];
     p.scale = scale;
     host_split_scale(scale, p.p2, p.rr);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
 #if !(XB_ABL & 16)
     attn_stats_kernel<<<dim3((unsigned)(((int64_t)B2 * N + 3) / 4)), dim3(256), 0, st>>>(p);
 #endif
@@ -343,12 +342,11 @@ extern "C" int gf_attn_cross_bwd(const void* qk, const void* v, const void* o, c
     (void)hipGetDevice(&dev);
     if (dev >= 64 || !((attr_set >> dev) & 1ull)) {
         for (auto k : kern) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
+            if (int e = gf_allow_lds(k, lds)) return e;
         }
         if (dev < 64) attr_set |= 1ull << dev;
     }
     const int total = ((N + 127) / 128) * H * B2;
     kern[p.rr == 1.f ? 1 : 0]<<<dim3(total), dim3(256), lds, st>>>(p);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

@@ -2,7 +2,7 @@
 // attention.hip dispatches to, the row store of a transposed accumulator and the bf16 LDS-DMA / transposing-read helpers.
 // Everything is static / in a named namespace so that every translation unit can include it.
 #pragma once
-#include "gf_common.h"
+#include "gf_launch.h"
 #include <cmath>
 
 namespace gfattn {
@@ -257,9 +257,7 @@ __device__ __forceinline__ bf16x8 scale_frag(bf16x8 v, float p2) {
 // opt in to more than 48 KiB of dynamic LDS
 template <typename K> int set_lds(K kern, size_t bytes) {
     if (bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return (int)e;
+        if (int e = gf_allow_lds(kern, bytes)) return e;
     }
     return 0;
 }

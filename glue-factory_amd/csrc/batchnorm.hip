@@ -7,8 +7,7 @@
 // workgroup, LDS combine, per-block partials -> host-side tiny sum / all-reduce for SyncBN) and
 // one fused normalise+affine+ReLU pass; the backward mirrors it (sum dz, sum dz*xhat, then dx).
 // T in / T out, fp32 statistics.
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -145,7 +144,7 @@ int launch_colsum(const void* x, const void* dy, const float* mean, const float*
     size_t lds = 256 * 2 * VEC * sizeof(float);
     bn_colsum_kernel<T, MODE><<<bn_blocks(M), 256, lds, st>>>(reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(dy),
                                                               mean, rstd, gamma, beta, part, M, C, relu);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 template <typename T, int MODE>
 int launch_apply(const void* x, const void* dy, const float* mean, const float* rstd, const float* gamma,
@@ -156,7 +155,7 @@ int launch_apply(const void* x, const void* dy, const float* mean, const float* 
     int nb = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
     bn_apply_kernel<T, MODE><<<nb, 256, 0, st>>>(reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(dy), mean, rstd,
                                                  gamma, beta, m1, m2, reinterpret_cast<T*>(out), M, C, relu);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 
@@ -330,93 +329,89 @@ extern "C" int gf_bn_nblk(int M) { return bn_blocks(M); }
 extern "C" int gf_bn_pack_sums(const float* part, int sets, int nblk, int C, float n_local, float* packed, float* local_copy,
                                void* stream) {
     if (sets <= 0 || sets > 65535 || nblk <= 0 || C <= 0 || n_local < 0.f || part == nullptr || packed == nullptr) return GF_ERR_SHAPE;
-    bn_pack_sums_kernel<<<dim3((C + 31) / 32, sets), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    bn_pack_sums_kernel<<<dim3((C + 31) / 32, sets), dim3(256), 0, gf_stream(stream)>>>(
         part, sets, nblk, C, n_local, packed, local_copy);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_bn_finalize_sets_fwd(const float* packed, int sets, int C, float eps, float momentum, float* mvr,
                                        float* run_mean, float* run_var, void* stream) {
     if (sets <= 0 || C <= 0 || packed == nullptr || mvr == nullptr) return GF_ERR_SHAPE;
     if ((run_mean == nullptr) != (run_var == nullptr)) return GF_ERR_SHAPE;
-    bn_finalize_sets_fwd_kernel<<<dim3((C + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    bn_finalize_sets_fwd_kernel<<<dim3((C + 255) / 256), dim3(256), 0, gf_stream(stream)>>>(
         packed, sets, C, eps, momentum, mvr, run_mean, run_var);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_bn_finalize_sets_bwd(const float* packed, const float* counts, int sets, int C, float* m12, void* stream) {
     if (sets <= 0 || C <= 0 || packed == nullptr || counts == nullptr || m12 == nullptr) return GF_ERR_SHAPE;
-    bn_finalize_sets_bwd_kernel<<<dim3((C + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    bn_finalize_sets_bwd_kernel<<<dim3((C + 255) / 256), dim3(256), 0, gf_stream(stream)>>>(
         packed, counts, sets, C, m12);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_bn_replay_running_n(const float* mvr, const float* counts, int sets, int C, float momentum, float* run_mean,
                                       float* run_var, const float* skip, void* stream) {
     if (sets <= 0 || C <= 0 || mvr == nullptr || counts == nullptr || run_mean == nullptr || run_var == nullptr) return GF_ERR_SHAPE;
-    bn_replay_running_n_kernel<<<dim3((C + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    bn_replay_running_n_kernel<<<dim3((C + 255) / 256), dim3(256), 0, gf_stream(stream)>>>(
         mvr, counts, sets, C, momentum, run_mean, run_var, skip);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_bn_stats(const void* x, float* part, int M, int C, int dtype, void* stream) {
     if (M <= 0 || C <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_F32) return launch_colsum<float, 0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, part, M, C, 0, st);
-    if (dtype == GF_BF16) return launch_colsum<bf16_t, 0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, part, M, C, 0, st);
-    return GF_ERR_DTYPE;
+    return gf_by_dtype(dtype, [&](auto t) {
+        return launch_colsum<decltype(t), 0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, part, M, C, 0, gf_stream(stream));
+    });
 }
 
 extern "C" int gf_bn_act_fwd(const void* x, const float* mean, const float* rstd, const float* gamma,
                              const float* beta, void* y, int M, int C, int relu, int dtype, void* stream) {
     if (M <= 0 || C <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_F32) return launch_apply<float, 0>(x, nullptr, mean, rstd, gamma, beta, nullptr, nullptr, y, M, C, relu, st);
-    if (dtype == GF_BF16) return launch_apply<bf16_t, 0>(x, nullptr, mean, rstd, gamma, beta, nullptr, nullptr, y, M, C, relu, st);
-    return GF_ERR_DTYPE;
+    return gf_by_dtype(dtype, [&](auto t) {
+        return launch_apply<decltype(t), 0>(x, nullptr, mean, rstd, gamma, beta, nullptr, nullptr, y, M, C, relu, gf_stream(stream));
+    });
 }
 
 extern "C" int gf_bn_bwd_stats(const void* x, const void* dy, const float* mean, const float* rstd,
                                const float* gamma, const float* beta, float* part, int M, int C, int relu,
                                int dtype, void* stream) {
     if (M <= 0 || C <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_F32) return launch_colsum<float, 1>(x, dy, mean, rstd, gamma, beta, part, M, C, relu, st);
-    if (dtype == GF_BF16) return launch_colsum<bf16_t, 1>(x, dy, mean, rstd, gamma, beta, part, M, C, relu, st);
-    return GF_ERR_DTYPE;
+    return gf_by_dtype(dtype, [&](auto t) {
+        return launch_colsum<decltype(t), 1>(x, dy, mean, rstd, gamma, beta, part, M, C, relu, gf_stream(stream));
+    });
 }
 
 extern "C" int gf_bn_bwd_dx(const void* x, const void* dy, const float* mean, const float* rstd,
                             const float* gamma, const float* beta, const float* m1, const float* m2,
                             void* dx, int M, int C, int relu, int dtype, void* stream) {
     if (M <= 0 || C <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_F32) return launch_apply<float, 1>(x, dy, mean, rstd, gamma, beta, m1, m2, dx, M, C, relu, st);
-    if (dtype == GF_BF16) return launch_apply<bf16_t, 1>(x, dy, mean, rstd, gamma, beta, m1, m2, dx, M, C, relu, st);
-    return GF_ERR_DTYPE;
+    return gf_by_dtype(dtype, [&](auto t) {
+        return launch_apply<decltype(t), 1>(x, dy, mean, rstd, gamma, beta, m1, m2, dx, M, C, relu, gf_stream(stream));
+    });
 }
 
 extern "C" int gf_bn_finalize_fwd(const float* part, int nblk, int C, float n, float eps, float momentum,
                                   float* mean, float* var, float* rstd, float* run_mean, float* run_var, void* stream) {
     if (nblk <= 0 || C <= 0 || n <= 0.f) return GF_ERR_SHAPE;
     if ((run_mean == nullptr) != (run_var == nullptr)) return GF_ERR_SHAPE;
-    bn_finalize_fwd_kernel<<<dim3((C + 31) / 32), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    bn_finalize_fwd_kernel<<<dim3((C + 31) / 32), dim3(256), 0, gf_stream(stream)>>>(
         part, nblk, C, n, eps, momentum, mean, var, rstd, run_mean, run_var);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_bn_replay_running(const float* mvr, int sets, int C, float n, float momentum, float* run_mean,
                                     float* run_var, const float* skip, void* stream) {
     if (sets <= 0 || C <= 0 || n <= 0.f || mvr == nullptr || run_mean == nullptr || run_var == nullptr) return GF_ERR_SHAPE;
-    bn_replay_running_kernel<<<dim3((C + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    bn_replay_running_kernel<<<dim3((C + 255) / 256), dim3(256), 0, gf_stream(stream)>>>(
         mvr, sets, C, n, momentum, run_mean, run_var, skip);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_bn_finalize_bwd(const float* part, int nblk, int C, float n, float* dbeta, float* dgamma,
                                   float* m1, float* m2, void* stream) {
     if (nblk <= 0 || C <= 0 || n <= 0.f) return GF_ERR_SHAPE;
-    bn_finalize_bwd_kernel<<<dim3((C + 31) / 32), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    bn_finalize_bwd_kernel<<<dim3((C + 31) / 32), dim3(256), 0, gf_stream(stream)>>>(
         part, nblk, C, 1.f / n, dbeta, dgamma, m1, m2);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

@@ -9,8 +9,7 @@
 // through LDS in the operand's OWN orientation (16-byte loads and stores either way; a row-contiguous operand is
 // transposed by the fragment reads: ds_read_b64_tr_b16 / 32-bit reads); the global loads of step t+1 are in flight
 // (registers) while step t is multiplied.  Scalar guarded loads on ragged edges and for operands without a unit stride.
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -182,14 +181,16 @@ __global__ __launch_bounds__(256) void bgemm_kernel(BgemmParams p) {
 }
 
 template <typename T>
-void bgemm_launch(const BgemmParams& p, hipStream_t st) {
+int bgemm_launch(const BgemmParams& p, hipStream_t st) {
     const dim3 grid((p.N + 127) / 128, (p.M + 127) / 128, p.batch);
     const size_t lds = 2 * BG<T>::TILE * sizeof(T);
     const bool akc = !(p.sai == 1 && p.sak != 1), bkc = !(p.sbj == 1 && p.sbk != 1);
-    if (akc && bkc) bgemm_kernel<T, true, true><<<grid, dim3(256), lds, st>>>(p);
-    else if (akc) bgemm_kernel<T, true, false><<<grid, dim3(256), lds, st>>>(p);
-    else if (bkc) bgemm_kernel<T, false, true><<<grid, dim3(256), lds, st>>>(p);
-    else bgemm_kernel<T, false, false><<<grid, dim3(256), lds, st>>>(p);
+    return gf_by_bool(akc, [&](auto ak) {
+        return gf_by_bool(bkc, [&](auto bk) {
+            bgemm_kernel<T, decltype(ak)::value, decltype(bk)::value><<<grid, dim3(256), lds, st>>>(p);
+            return gf_launched();
+        });
+    });
 }
 
 }  // namespace
@@ -204,9 +205,5 @@ extern "C" int gf_bgemm(const void* a, const void* b, void* c, int batch, int M,
     p.sab = a_strides[0]; p.sai = a_strides[1]; p.sak = a_strides[2];
     p.sbb = b_strides[0]; p.sbk = b_strides[1]; p.sbj = b_strides[2];
     p.scb = c_strides[0]; p.sci = c_strides[1]; p.scj = c_strides[2];
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_F32) bgemm_launch<float>(p, st);
-    else if (dtype == GF_BF16) bgemm_launch<bf16_t>(p, st);
-    else return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) { return bgemm_launch<decltype(t)>(p, gf_stream(stream)); });
 }

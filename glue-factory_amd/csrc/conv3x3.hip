@@ -18,8 +18,7 @@
 //   * output channels on the MFMA i axis (registers), pixels on lanes: a lane ends with 64 channels of two pixels;
 //     bias / ReLU / BN affine are lane-local, the bf16 result goes through an LDS tile so that the store (and the
 //     2x2 max-pool) is done by the whole workgroup in whole 128-byte pixels.
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 #ifndef C3_ABL          // probe builds only (tools/probe): bit 0 no tail+store, 1 no DMA in the loop, 2 no MFMA loop, 3 no global store
 #define C3_ABL 0
@@ -354,7 +353,7 @@ extern "C" int gf_conv3x3_c64_ld(const void* x, const void* w, const float* bias
     if ((int64_t)H * W * 128 >= (1ll << 31)) return GF_ERR_UNSUPPORTED;      // 32-bit byte offsets inside one image (buffer loads)
     if (ldy < 64 || ldy % 8) return GF_ERR_ALIGN;                            // whole 16-byte chunks of a pixel
     // 16-byte loads of x (LDS-DMA pieces) and w (weight fragments), 16-byte stores through y
-    if ((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(w) | reinterpret_cast<size_t>(y)) & 15) return GF_ERR_ALIGN;
+    if (!gf_aligned16(x, w, y)) return GF_ERR_ALIGN;
     if ((int64_t)H * W * ldy >= (1ll << 31)) return GF_ERR_UNSUPPORTED;      // (32-bit element offsets inside one output image)
     C3Params p;
     p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(w); p.bias = bias; p.scale = scale; p.shift = shift;
@@ -362,11 +361,10 @@ extern "C" int gf_conv3x3_c64_ld(const void* x, const void* w, const float* bias
     const size_t lds = C3_LDS;
     const int tiles = (W / C3_TW) * (H / C3_TH) * B;
     const int grid = tiles < 256 ? tiles : 256;            // one persistent workgroup per CU
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     void (*k)(C3Params) = pool ? (relu ? conv3x3_c64_kernel<true, true> : conv3x3_c64_kernel<true, false>)
                                : (relu ? conv3x3_c64_kernel<false, true> : conv3x3_c64_kernel<false, false>);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
+    if (int e = gf_allow_lds(k, lds)) return e;
     k<<<dim3(grid), 256, lds, st>>>(p);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

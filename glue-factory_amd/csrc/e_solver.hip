@@ -280,7 +280,7 @@ extern "C" int gf_e_ransac(const float* pts0n, const float* pts1n, const int64_t
     if (lo_iters < 0 || lo_iters > 64) return GF_ERR_SHAPE;
     Ws w;
     carve(ws, B, M, T, &w);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     const int nblk = (int)nblk_of(T), nsb = (T + SOLVE_LANES - 1) / SOLVE_LANES;
     e_compact_kernel<<<dim3(B), dim3(256), 0, st>>>(pts0n, pts1n, matches0, w, M, N);
     e_solve_kernel<<<dim3((unsigned)(B * nsb)), dim3(SOLVE_LANES), 0, st>>>(w, M, T, nsb, seed, samples, cand, ncand);
@@ -291,7 +291,7 @@ extern "C" int gf_e_ransac(const float* pts0n, const float* pts1n, const int64_t
         e_rescore_kernel<<<dim3(B), dim3(256), 0, st>>>(w, th, M);
     }
     e_pose_kernel<<<dim3(B), dim3(256), 0, st>>>(w, M, 1, nullptr, nullptr, E, R, t, inliers, num_inliers, success, nullptr);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_e_pose(const float* pts0n, const float* pts1n, const int64_t* matches0, const uint8_t* inliers,
@@ -301,8 +301,8 @@ extern "C" int gf_e_pose(const float* pts0n, const float* pts1n, const int64_t* 
     if (inliers == nullptr || E == nullptr || R == nullptr || t == nullptr || num_front == nullptr) return GF_ERR_SHAPE;
     Ws w;
     carve(ws, B, M, 1, &w);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     e_compact_kernel<<<dim3(B), dim3(256), 0, st>>>(pts0n, pts1n, matches0, w, M, N);
     e_pose_kernel<<<dim3(B), dim3(256), 0, st>>>(w, M, 0, E, inliers, nullptr, R, t, nullptr, nullptr, nullptr, num_front);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

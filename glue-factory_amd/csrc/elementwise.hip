@@ -4,8 +4,7 @@
 //   * LayerNorm(affine) + exact GELU of the FFN hidden, forward and backward
 //     (reference: lightglue.py:143-148, the ffn.1 / ffn.2 modules).
 // One wave per row/token, 4 waves per workgroup, grid-stride; fp32 math, T in / T out.
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -390,7 +389,7 @@ int ln_fwd_t(const void* x, const float* gamma, const float* beta, void* y, floa
         default: return GF_ERR_UNSUPPORTED;
     }
 #undef GF_LN_FWD
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 template <typename T>
@@ -412,7 +411,7 @@ int ln_bwd_t(const void* x, const float* gamma, const float* beta, const float* 
         default: if (full) GF_LN_BWD(4, true); else GF_LN_BWD(4, false); break;
     }
 #undef GF_LN_BWD
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 }  // namespace
@@ -426,37 +425,35 @@ static bool rotary_vec_ok(int H, int D) {
 extern "C" int gf_rotary_qk(void* qkv, const float* cs, int B, int N, int H, int D, int inverse,
                             int dtype, void* stream) {
     if (B <= 0 || N <= 0 || H <= 0 || D <= 0 || (D & 1)) return GF_ERR_SHAPE;
-    if (dtype != GF_F32 && dtype != GF_BF16) return GF_ERR_DTYPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     int64_t tokens = (int64_t)B * N;
     int nb = (int)((tokens + 3) / 4 > 8192 ? 8192 : (tokens + 3) / 4);
     const bool vec = rotary_vec_ok(H, D);
-#define GF_ROT(K, T, INV) K<T, INV, false><<<nb, 256, 0, st>>>((T*)qkv, nullptr, cs, nullptr, nullptr, tokens, H, D)
-    if (dtype == GF_F32) {
-        if (vec) { if (inverse) GF_ROT(rotary_vec_kernel, float, true); else GF_ROT(rotary_vec_kernel, float, false); }
-        else { if (inverse) GF_ROT(rotary_kernel, float, true); else GF_ROT(rotary_kernel, float, false); }
-    } else {
-        if (vec) { if (inverse) GF_ROT(rotary_vec_kernel, bf16_t, true); else GF_ROT(rotary_vec_kernel, bf16_t, false); }
-        else { if (inverse) GF_ROT(rotary_kernel, bf16_t, true); else GF_ROT(rotary_kernel, bf16_t, false); }
-    }
-#undef GF_ROT
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return gf_by_bool(inverse, [&](auto inv) {
+            constexpr bool INV = decltype(inv)::value;
+            if (vec) rotary_vec_kernel<T, INV, false><<<nb, 256, 0, st>>>((T*)qkv, nullptr, cs, nullptr, nullptr, tokens, H, D);
+            else rotary_kernel<T, INV, false><<<nb, 256, 0, st>>>((T*)qkv, nullptr, cs, nullptr, nullptr, tokens, H, D);
+            return gf_launched();
+        });
+    });
 }
 
 extern "C" int gf_rotary_qk_bwd(void* dqkv, const void* qkv_rot, const float* cs, float* dtheta, const float* dtheta_base,
                                 int B, int N, int H, int D, int dtype, void* stream) {
     if (B <= 0 || N <= 0 || H <= 0 || D <= 0 || (D & 1)) return GF_ERR_SHAPE;
     if (D > 64 && D != 128) return GF_ERR_UNSUPPORTED;  // the q/k pair reduction stays inside one wave pass (<= 64) or one lane (128)
-    if (dtype != GF_F32 && dtype != GF_BF16) return GF_ERR_DTYPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     int64_t tokens = (int64_t)B * N;
     int nb = (int)((tokens + 3) / 4 > 8192 ? 8192 : (tokens + 3) / 4);
     const bool vec = rotary_vec_ok(H, D);
-#define GF_ROTB(K, T) K<T, true, true><<<nb, 256, 0, st>>>((T*)dqkv, (const T*)qkv_rot, cs, dtheta, dtheta_base, tokens, H, D)
-    if (dtype == GF_F32) { if (vec) GF_ROTB(rotary_vec_kernel, float); else GF_ROTB(rotary_kernel, float); }
-    else { if (vec) GF_ROTB(rotary_vec_kernel, bf16_t); else GF_ROTB(rotary_kernel, bf16_t); }
-#undef GF_ROTB
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (vec) rotary_vec_kernel<T, true, true><<<nb, 256, 0, st>>>((T*)dqkv, (const T*)qkv_rot, cs, dtheta, dtheta_base, tokens, H, D);
+        else rotary_kernel<T, true, true><<<nb, 256, 0, st>>>((T*)dqkv, (const T*)qkv_rot, cs, dtheta, dtheta_base, tokens, H, D);
+        return gf_launched();
+    });
 }
 
 extern "C" int gf_ln_gelu_nblk(int R) { return ln_blocks(R); }
@@ -464,18 +461,16 @@ extern "C" int gf_ln_gelu_nblk(int R) { return ln_blocks(R); }
 extern "C" int gf_ln_gelu_fwd(const void* x, const float* gamma, const float* beta, void* y,
                               float* mean, float* rstd, int R, int C, float eps, int dtype, void* stream) {
     if (R <= 0 || C <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_F32) return ln_fwd_t<float>(x, gamma, beta, y, mean, rstd, R, C, eps, st);
-    if (dtype == GF_BF16) return ln_fwd_t<bf16_t>(x, gamma, beta, y, mean, rstd, R, C, eps, st);
-    return GF_ERR_DTYPE;
+    return gf_by_dtype(dtype, [&](auto t) {
+        return ln_fwd_t<decltype(t)>(x, gamma, beta, y, mean, rstd, R, C, eps, gf_stream(stream));
+    });
 }
 
 extern "C" int gf_ln_gelu_bwd(const void* x, const float* gamma, const float* beta, const float* mean,
                               const float* rstd, const void* dy, void* dx, float* dgamma_part,
                               float* dbeta_part, int R, int C, int dtype, void* stream) {
     if (R <= 0 || C <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_F32) return ln_bwd_t<float>(x, gamma, beta, mean, rstd, dy, dx, dgamma_part, dbeta_part, R, C, st);
-    if (dtype == GF_BF16) return ln_bwd_t<bf16_t>(x, gamma, beta, mean, rstd, dy, dx, dgamma_part, dbeta_part, R, C, st);
-    return GF_ERR_DTYPE;
+    return gf_by_dtype(dtype, [&](auto t) {
+        return ln_bwd_t<decltype(t)>(x, gamma, beta, mean, rstd, dy, dx, dgamma_part, dbeta_part, R, C, gf_stream(stream));
+    });
 }

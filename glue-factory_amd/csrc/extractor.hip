@@ -4,14 +4,12 @@
 //       one pass over the channels-last activation instead of bias-add, clamp, batch-norm and pool passes;
 //   * simple_nms (:19-34): five 2r+1 max-pools and a dozen elementwise passes over the [B,H,W] score map
 //       become one kernel working on a register tile (64 columns x 48 + 10r rows per wave) with a 5r halo.
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-template <typename T> struct V16 { static constexpr int N = 16 / sizeof(T); };
 
 template <typename T> __device__ __forceinline__ void ld_vec(float (&x)[16 / sizeof(T)], const T* p) {
     union { u32x4 u; T e[16 / sizeof(T)]; } v;
@@ -31,7 +29,7 @@ template <typename T, bool RELU>
 __global__ __launch_bounds__(256) void bias_act_bn_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                           const float* __restrict__ bias, const float* __restrict__ scale,
                                                           const float* __restrict__ shift, int64_t nvec, int C) {
-    constexpr int VEC = V16<T>::N;
+    constexpr int VEC = Vec16<T>::N;
     const int cv = C / VEC;                                   // vectors per pixel
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
         const int c0 = (int)(i % cv) * VEC;
@@ -53,7 +51,7 @@ __global__ __launch_bounds__(256) void bias_act_bn_pool_kernel(const T* __restri
                                                                const float* __restrict__ bias, const float* __restrict__ scale,
                                                                const float* __restrict__ shift, int64_t nvec_out,
                                                                int H, int W, int C) {
-    constexpr int VEC = V16<T>::N;
+    constexpr int VEC = Vec16<T>::N;
     const int cv = C / VEC, Wo = W / 2, Ho = H / 2;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec_out; i += (int64_t)gridDim.x * 256) {
         const int c0 = (int)(i % cv) * VEC;
@@ -425,7 +423,7 @@ template <int R> int nms_launch(const float* s, float* out, int B, int H, int W,
     const dim3 grid((tiles + 3) / 4, B);
     if (cand_idx) nms_reg_kernel<R, true><<<grid, dim3(256), 0, st>>>(s, out, H, W, border, strips, tiles, cand_idx);
     else nms_reg_kernel<R, false><<<grid, dim3(256), 0, st>>>(s, out, H, W, border, strips, tiles, nullptr);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 // ---- descriptor sampling -------------------------------------------------------------------------
@@ -518,49 +516,48 @@ __global__ __launch_bounds__(256) void detector_scores_kernel(const T* __restric
 extern "C" int gf_bias_act_bn_nhwc(const void* x, void* y, const float* bias, const float* scale, const float* shift,
                                    int B, int H, int W, int C, int relu, int pool, int dtype, void* stream) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return GF_ERR_SHAPE;
-    if (dtype != GF_F32 && dtype != GF_BF16) return GF_ERR_DTYPE;
-    const int vec = dtype == GF_BF16 ? 8 : 4;
-    if (C % vec) return GF_ERR_ALIGN;
-    if (pool && ((H | W) & 1)) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int64_t npix = (int64_t)B * (pool ? (H / 2) * (int64_t)(W / 2) : (int64_t)H * W);
-    const int64_t nvec = npix * (C / vec);
-    const int64_t want = (nvec + 255) / 256;
-    const int nb = (int)(want > 16384 ? 16384 : want);
-#define GF_BAB(T, RELU)                                                                                              \
-    if (pool)                                                                                                        \
-        bias_act_bn_pool_kernel<T, RELU><<<nb, 256, 0, st>>>((const T*)x, (T*)y, bias, scale, shift, nvec, H, W, C); \
-    else                                                                                                             \
-        bias_act_bn_kernel<T, RELU><<<nb, 256, 0, st>>>((const T*)x, (T*)y, bias, scale, shift, nvec, C);
-    if (dtype == GF_BF16) { if (relu) { GF_BAB(bf16_t, true) } else { GF_BAB(bf16_t, false) } }
-    else { if (relu) { GF_BAB(float, true) } else { GF_BAB(float, false) } }
-#undef GF_BAB
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        constexpr int vec = Vec16<T>::N;
+        if (C % vec) return GF_ERR_ALIGN;
+        if (pool && ((H | W) & 1)) return GF_ERR_SHAPE;
+        hipStream_t st = gf_stream(stream);
+        const int64_t npix = (int64_t)B * (pool ? (H / 2) * (int64_t)(W / 2) : (int64_t)H * W);
+        const int64_t nvec = npix * (C / vec);
+        const int64_t want = (nvec + 255) / 256;
+        const int nb = (int)(want > 16384 ? 16384 : want);
+        return gf_by_bool(relu, [&](auto r) {
+            constexpr bool RELU = decltype(r)::value;
+            if (pool)
+                bias_act_bn_pool_kernel<T, RELU><<<nb, 256, 0, st>>>((const T*)x, (T*)y, bias, scale, shift, nvec, H, W, C);
+            else
+                bias_act_bn_kernel<T, RELU><<<nb, 256, 0, st>>>((const T*)x, (T*)y, bias, scale, shift, nvec, C);
+            return gf_launched();
+        });
+    });
 }
 
 extern "C" int gf_detector_scores(const void* y, const float* bias, const float* scale, const float* shift, float* scores,
                                   int B, int h, int w, int relu, int dtype, void* stream) {
     if (B <= 0 || h <= 0 || w <= 0) return GF_ERR_SHAPE;
-    if ((reinterpret_cast<size_t>(y) | reinterpret_cast<size_t>(scores)) & 15) return GF_ERR_ALIGN;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (!gf_aligned16(y, scores)) return GF_ERR_ALIGN;
     const int64_t cells = (int64_t)B * h * w;
     const dim3 grid((unsigned)((cells + 255) / 256));
-    if (dtype == GF_BF16) {
-        detector_scores_kernel<bf16_t><<<grid, 256, 256 * 65 * sizeof(bf16_t), st>>>((const bf16_t*)y, bias, scale, shift, scores, cells, h, w, relu);
-    } else if (dtype == GF_F32) {
-        const int lds = 256 * 65 * (int)sizeof(float);
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(detector_scores_kernel<float>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        detector_scores_kernel<float><<<grid, 256, lds, st>>>((const float*)y, bias, scale, shift, scores, cells, h, w, relu);
-    } else return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const size_t lds = 256 * 65 * sizeof(T);
+        if constexpr (sizeof(T) == 4) {            // 65 KiB of fp32 needs the opt-in; bf16's 32.5 KiB does not
+            if (int e = gf_allow_lds(detector_scores_kernel<T>, lds)) return e;
+        }
+        detector_scores_kernel<T><<<grid, 256, lds, gf_stream(stream)>>>((const T*)y, bias, scale, shift, scores, cells, h, w, relu);
+        return gf_launched();
+    });
 }
 
 extern "C" int gf_nms_scores(const float* scores, float* out, int B, int H, int W, int radius, int border,
                              void* stream) {
     if (B <= 0 || H <= 0 || W <= 0 || border < 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     switch (radius) {
         case 1: return nms_launch<1>(scores, out, B, H, W, border, st);
         case 2: return nms_launch<2>(scores, out, B, H, W, border, st);
@@ -587,7 +584,7 @@ extern "C" int gf_nms_candidates(const float* scores, float* cand_scores, int* c
                                  int border, void* stream) {
     if (B <= 0 || H <= 0 || W <= 0 || border < 0) return GF_ERR_SHAPE;
     if ((int64_t)H * W > 0x7fffffff) return GF_ERR_UNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     switch (radius) {
         case 1: return nms_launch<1>(scores, cand_scores, B, H, W, border, st, cand_idx);
         case 2: return nms_launch<2>(scores, cand_scores, B, H, W, border, st, cand_idx);
@@ -601,16 +598,13 @@ extern "C" int gf_sample_descriptors(const void* map, const float* kpts, float* 
                                      int stride, int dtype, void* stream) {
     if (B <= 0 || N <= 0 || h <= 0 || w <= 0 || stride <= 0) return GF_ERR_SHAPE;
     if (C <= 0 || C % 64 || C > 512) return GF_ERR_ALIGN;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)B * N;
     const dim3 grid((unsigned)((total + 3) / 4));
-    if (dtype == GF_BF16)
-        sample_desc_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)map, kpts, out, total, N, h, w, C, 1.f / stride);
-    else if (dtype == GF_F32)
-        sample_desc_kernel<float><<<grid, 256, 0, st>>>((const float*)map, kpts, out, total, N, h, w, C, 1.f / stride);
-    else
-        return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        sample_desc_kernel<T><<<grid, 256, 0, gf_stream(stream)>>>((const T*)map, kpts, out, total, N, h, w, C, 1.f / stride);
+        return gf_launched();
+    });
 }
 
 extern "C" int gf_conv1_bias_act_bn(const void* img, const void* w, const float* bias, const float* scale,
@@ -618,12 +612,13 @@ extern "C" int gf_conv1_bias_act_bn(const void* img, const void* w, const float*
                                     void* stream) {
     if (B <= 0 || H <= 0 || W <= 0) return GF_ERR_SHAPE;
     if (C != 64) return GF_ERR_UNSUPPORTED;
-    if (dtype != GF_F32 && dtype != GF_BF16) return GF_ERR_DTYPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((W + 32 * C1_NX - 1) / (32 * C1_NX), (H + C1_TY - 1) / C1_TY, B);
-#define GF_C1(T, RELU) conv1_fused_kernel<T, RELU, 64><<<grid, 256, 0, st>>>((const T*)img, (const T*)w, bias, scale, shift, (T*)out, H, W)
-    if (dtype == GF_BF16) { if (relu) GF_C1(bf16_t, true); else GF_C1(bf16_t, false); }
-    else { if (relu) GF_C1(float, true); else GF_C1(float, false); }
-#undef GF_C1
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return gf_by_bool(relu, [&](auto r) {
+            conv1_fused_kernel<T, decltype(r)::value, 64><<<grid, 256, 0, gf_stream(stream)>>>(
+                (const T*)img, (const T*)w, bias, scale, shift, (T*)out, H, W);
+            return gf_launched();
+        });
+    });
 }

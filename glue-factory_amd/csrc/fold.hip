@@ -12,8 +12,7 @@
 //   gf_fold_linear_bwd   from the gradient g of the stacked weight and gb of the folded bias:
 //                        dW0 = [g_a | g_c Wo[:, cperm]^T + gb bo^T],  dWo[:, cperm] = W0b^T g_c,  dbo = W0b^T gb  (db0 = gb).
 // Exact fp32 FMA arithmetic (the compute-dtype rounding happens once, in the cast launch).
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -215,9 +214,9 @@ extern "C" int gf_fold_entry_bytes(void) { return (int)sizeof(FoldEntry); }
 
 extern "C" int gf_fold_linear_fwd(const void* table, int n_entries, int total_tiles, void* stream) {
     if (n_entries <= 0 || total_tiles <= 0) return GF_ERR_SHAPE;
-    fold_fwd_kernel<<<dim3(total_tiles), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    fold_fwd_kernel<<<dim3(total_tiles), dim3(256), 0, gf_stream(stream)>>>(
         static_cast<const FoldEntry*>(table), n_entries);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_fold_linear_bwd(const float* g, const float* gb, const float* W0, const float* Wo, const float* bo,
@@ -232,6 +231,6 @@ extern "C" int gf_fold_linear_bwd(const float* g, const float* gb, const float* 
     p.tiles_a = ((R + 63) / 64) * ((c0 + 63) / 64);             // copy tiles 64 x 64, product tiles BT x BT
     p.tiles_b = ((R + BT - 1) / BT) * ((K + BT - 1) / BT);
     p.tiles_c = ((K + BT - 1) / BT) * ((N + BT - 1) / BT + 1);
-    fold_bwd_kernel<<<dim3(p.tiles_a + p.tiles_b + p.tiles_c), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(p);
-    return (int)hipGetLastError();
+    fold_bwd_kernel<<<dim3(p.tiles_a + p.tiles_b + p.tiles_c), dim3(256), 0, gf_stream(stream)>>>(p);
+    return gf_launched();
 }

@@ -18,8 +18,7 @@
 //     and stores retire through ONE in-order counter on this part, so their program order is fixed by hand
 //     (inline asm) and every wait is a counted vmcnt: residual(t), DMA(t + 2), MFMAs(t), stores(t).
 #include <type_traits>
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -272,12 +271,10 @@ bool gs_serves(int M, int N, int K0, int K1, bool cs, int rot_n, bool res, bool 
 template <int KF, bool TWO, int RES, bool ROT = false>
 int gs_launch(const GsParams& p, hipStream_t st) {
     const size_t lds = (size_t)GS_NSTAGE * GS_TILE;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_st_kernel<KF, TWO, RES, ROT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
+    if (int e = gf_allow_lds(gemm_st_kernel<KF, TWO, RES, ROT>, lds)) return e;
     const GsGrid g = gs_grid(p.M, p.N, 16 * KF);
     gemm_st_kernel<KF, TWO, RES, ROT><<<dim3(g.gx, g.gy), dim3(512), lds, st>>>(p);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 }  // namespace

@@ -24,8 +24,7 @@
 // The rotary epilogue (lightglue.py:42-49,159-160) rotates channel pairs of the q and k thirds of the fused Wqkv
 // output by the cached (cos, sin) table while the tile is still in fp32.
 // T = float runs the same code on v_mfma_f32_32x32x2_f32 (exact fp32, parity mode).
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -364,12 +363,10 @@ template <typename T, int KF, bool TWO> int gw_launch(const GwParams& p, hipStre
     constexpr GwShape S = gw_shape((int)sizeof(T), 16 * KF);
     constexpr int ROWB = 16 * KF * (int)sizeof(T);
     const size_t lds = 2 * (size_t)(ROWB * 32 > 16384 ? ROWB * 32 : 16384) + S.NW * GW_SCRATCH + (size_t)p.N * 4;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ws_kernel<T, KF, S.R, TWO, S.NW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
+    if (int e = gf_allow_lds(gemm_ws_kernel<T, KF, S.R, TWO, S.NW>, lds)) return e;
     const GwGrid g = gw_grid(p.M, S);
     gemm_ws_kernel<T, KF, S.R, TWO, S.NW><<<dim3(g.grid), 64 * S.NW, lds, st>>>(p);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 template <typename T, bool TWO> int gw_dispatch(const GwParams& p, int K, hipStream_t st) {
@@ -459,7 +456,7 @@ extern "C" int gf_gemm_res2(const void* x0, const void* x1, const void* w, const
     if (K1 && !x1) return GF_ERR_UNSUPPORTED;
     if (ld0 % 8 || (K1 && ld1 % 8) || ldw % 8 || ldy % 8 || ldr % 8 || ldr_b % 8) return GF_ERR_ALIGN;
     return gf_gemm_stream_try(x0, x1, w, bias, res, y, nullptr, 0, M, N, K0, K1, ld0, ld1, ldw, ldr, ldy,
-                              reinterpret_cast<hipStream_t>(stream), res_b, ldr_b);
+                              gf_stream(stream), res_b, ldr_b);
 }
 
 extern "C" int gf_gemm(const void* x0, const void* x1, const void* w, const float* bias, const void* res, void* y,
@@ -468,17 +465,18 @@ extern "C" int gf_gemm(const void* x0, const void* x1, const void* w, const floa
     if (const int e = gw_check(M, N, K0, K1, dtype)) return e;
     const int K = K0 + K1;
     if (K1 && !x1) return GF_ERR_UNSUPPORTED;
-    const int al = dtype == GF_BF16 ? 8 : 4;                // 16-byte aligned rows of x / W / y / res
+    const int al = gf_vec_elems(dtype);                     // 16-byte aligned rows of x / W / y / res
     if (ld0 % al || (K1 && ld1 % al) || ldw % al || ldy % al || (res && ldr % al)) return GF_ERR_ALIGN;
     if (const int e = gw_check_rot(cs != nullptr, rot_n, N)) return e;
     GwParams p;
     p.x0 = x0; p.x1 = x1; p.w = w; p.bias = bias; p.res = res; p.y = y; p.cs = cs; p.rot_n = cs ? rot_n : 0;
     p.M = M; p.N = N; p.K0 = K0; p.K1 = K1; p.ld0 = ld0; p.ld1 = ld1; p.ldw = ldw; p.ldr = ldr; p.ldy = ldy;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     if (GW_STREAM && dtype == GF_BF16) {
         const int e = gf_gemm_stream_try(x0, x1, w, bias, res, y, cs, rot_n, M, N, K0, K1, ld0, ld1, ldw, ldr, ldy, st);
         if (e != GF_ERR_UNSUPPORTED) return e;
     }
-    if (dtype == GF_BF16) return K1 ? gw_dispatch<bf16_t, true>(p, K, st) : gw_dispatch<bf16_t, false>(p, K, st);
-    return K1 ? gw_dispatch<float, true>(p, K, st) : gw_dispatch<float, false>(p, K, st);
+    return gf_by_dtype(dtype, [&](auto t) {
+        return gf_by_bool(K1 != 0, [&](auto two) { return gw_dispatch<decltype(t), decltype(two)::value>(p, K, st); });
+    });
 }

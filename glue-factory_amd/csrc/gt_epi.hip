@@ -11,8 +11,7 @@
 //   l = F (x, y, 1)            the own point's line in the other image,  na = sqrtf(l0^2 + l1^2 + 1e-15f)
 //   nb = sqrtf((F^T p)0^2 + (F^T p)1^2 + 1e-15f)   for the other point p (the norm of ITS line in the own image)
 //   num = |p . l|,  d = 0.5f * (num / na + num / nb)
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -130,9 +129,9 @@ __global__ __launch_bounds__(256) void gt_depth_reward_kernel(
 extern "C" int gf_gt_epi_min(const float* own, const float* oth, const float* F, const uint8_t* own_flag,
                              const uint8_t* oth_flag, float* out_min, int B, int No, int Ns, void* stream) {
     if (B <= 0 || No <= 0 || Ns <= 0) return GF_ERR_SHAPE;
-    gt_epi_min_kernel<<<dim3((No + 255) / 256, B), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    gt_epi_min_kernel<<<dim3((No + 255) / 256, B), 256, 0, gf_stream(stream)>>>(
         own, oth, F, own_flag, oth_flag, out_min, No, Ns);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_gt_depth_reward(const float* kp0, const float* kp0_1, const float* kp1, const float* kp1_0,
@@ -141,7 +140,7 @@ extern "C" int gf_gt_depth_reward(const float* kp0, const float* kp0_1, const fl
                                   void* stream) {
     if (B <= 0 || M <= 0 || N <= 0) return GF_ERR_SHAPE;
     gt_depth_reward_kernel<<<dim3((N + 255) / 256, (M + REWARD_ROWS - 1) / REWARD_ROWS, B), 256, 0,
-                             reinterpret_cast<hipStream_t>(stream)>>>(kp0, kp0_1, kp1, kp1_0, vis0, vis1, F, flag0, flag1,
+                             gf_stream(stream)>>>(kp0, kp0_1, kp1, kp1_0, vis0, vis1, F, flag0, flag1,
                                                                       reward, pos_th2, neg_th, M, N);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

@@ -23,8 +23,7 @@
 // test_threshold_rounding, compares exactly this against the torch form on the device).
 #include <hip/hip_fp16.h>
 
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 #pragma clang fp contract(off)
 
@@ -99,8 +98,8 @@ extern "C" int gf_line_close_counts(const float* end, const uint16_t* dir, const
     const int ct = (C + LC_LINES - 1) / LC_LINES;
     if (B > 65535 || ct > 65535) return GF_ERR_UNSUPPORTED;      // grid limits of the y / z dimensions
     const float th = __half2float(__float2half_rn(dist_th));     // torch's rule: the scalar takes the tensor's type
-    line_close_counts_kernel<<<dim3((A + LC_SEGS - 1) / LC_SEGS, ct, B), LC_SEGS, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    line_close_counts_kernel<<<dim3((A + LC_SEGS - 1) / LC_SEGS, ct, B), LC_SEGS, 0, gf_stream(stream)>>>(
         end, reinterpret_cast<const __half*>(dir), reinterpret_cast<const __half*>(len), pts, keep, count, A, C, P, th,
         transposed);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

@@ -7,8 +7,7 @@
 // arg-mins.  Here one thread owns one point, streams the other image's points through LDS and
 // keeps (min dist, arg-min, min of its one-sided distance) in registers; called once per
 // direction.  Ties resolve to the lowest index (what torch's CPU min returns).
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -57,7 +56,7 @@ __global__ __launch_bounds__(256) void gt_nn_kernel(const float* __restrict__ ow
 extern "C" int gf_gt_nn(const float* own, const float* own_warped, const float* oth, const float* oth_warped,
                         int64_t* arg, float* dmin, float* own_min, int B, int No, int Ns, void* stream) {
     if (B <= 0 || No <= 0 || Ns <= 0) return GF_ERR_SHAPE;
-    gt_nn_kernel<<<dim3((No + 255) / 256, B), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    gt_nn_kernel<<<dim3((No + 255) / 256, B), 256, 0, gf_stream(stream)>>>(
         own, own_warped, oth, oth_warped, arg, dmin, own_min, No, Ns);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

@@ -244,7 +244,7 @@ extern "C" int gf_h_ransac(const float* kpts0, const float* kpts1, const int64_t
     if (!(ransac_th > 0.f) || !(ransac_th < 1e18f) || lo_iters < 0 || lo_iters > 64) return GF_ERR_SHAPE;
     Ws w;
     carve(ws, B, M, T, &w);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     const int nblk = nblk_of(T);
     const float th2 = ransac_th * ransac_th;
     h_compact_kernel<<<dim3(B), dim3(256), 0, st>>>(kpts0, kpts1, matches0, w, M, N);
@@ -255,7 +255,7 @@ extern "C" int gf_h_ransac(const float* kpts0, const float* kpts1, const int64_t
         h_rescore_kernel<<<dim3(B), dim3(256), 0, st>>>(w, M, th2);
     }
     h_final_kernel<<<dim3(B), dim3(256), 0, st>>>(w, M, 1, H, inliers, num_inliers, success);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_h_dlt(const float* kpts0, const float* kpts1, const int64_t* matches0, const float* weights, int B, int M,
@@ -264,10 +264,10 @@ extern "C" int gf_h_dlt(const float* kpts0, const float* kpts1, const int64_t* m
     if (H == nullptr || success == nullptr) return GF_ERR_SHAPE;
     Ws w;
     carve(ws, B, M, 1, &w);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     h_compact_kernel<<<dim3(B), dim3(256), 0, st>>>(kpts0, kpts1, matches0, w, M, N);
     h_refit_kernel<<<dim3(B), dim3(256), 0, st>>>(w, weights, M, 0, 0);
     h_final_kernel<<<dim3(B), dim3(256), 0, st>>>(w, M, 0, H, nullptr, nullptr, success);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 

@@ -1,6 +1,5 @@
 // Fused backward of the assignment head (gf_head_bwd).  Own translation unit with its own compiler flags (csrc/Makefile).
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 #include "attn_common.h"
 
 using namespace gfattn;
@@ -216,7 +215,7 @@ extern "C" int gf_head_bwd(const void* a, const void* b, const float* r, const f
                            void* da, void* db, int B, int M, int N, int D, int dtype, void* stream) {
     if (B <= 0 || M <= 0 || N <= 0) return GF_ERR_SHAPE;
     if (dtype != GF_BF16 || D != 256) return GF_ERR_UNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     const size_t lds = (size_t)HB_NSTAGE * HB_STAGE;
     if (int e = set_lds(head_bwd_bf16_kernel, lds)) return e;
     HeadBwdParams p;
@@ -224,10 +223,10 @@ extern "C" int gf_head_bwd(const void* a, const void* b, const float* r, const f
     p.own = static_cast<const bf16_t*>(b); p.oth = static_cast<const bf16_t*>(a); p.no = c; p.go = gc; p.ns = r; p.gs = gr;
     p.down = static_cast<bf16_t*>(db); p.B = B; p.No = N; p.Ns = M;
     head_bwd_bf16_kernel<<<dim3(((N + 127) / 128) * B), dim3(256), lds, st>>>(p);
-    if (int e = (int)hipGetLastError()) return e;
+    if (int e = gf_launched()) return e;
     // d md0: owner = md0 rows, streamed = md1 rows
     p.own = static_cast<const bf16_t*>(a); p.oth = static_cast<const bf16_t*>(b); p.no = r; p.go = gr; p.ns = c; p.gs = gc;
     p.down = static_cast<bf16_t*>(da); p.No = M; p.Ns = N;
     head_bwd_bf16_kernel<<<dim3(((M + 127) / 128) * B), dim3(256), lds, st>>>(p);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

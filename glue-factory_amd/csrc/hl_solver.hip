@@ -276,7 +276,7 @@ extern "C" int gf_hl_ransac(const float* kpts0, const float* kpts1, const int64_
     if (!(ransac_th > 0.f) || !(ransac_th < 1e18f) || lo_iters < 0 || lo_iters > 64) return GF_ERR_SHAPE;
     Ws w;
     carve(ws, B, M, L, T, &w);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     hl_compact_kernel<<<dim3(B), dim3(256), 0, st>>>(kpts0, kpts1, matches0, lines0, lines1, line_matches0, w, M, N, L, L1);
     hl_score_kernel<<<dim3((unsigned)(B * nblk)), dim3(256), 0, st>>>(w, M, L, T, (int)nblk, ransac_th, seed, samples, hyp_H,
                                                                       hyp_counts);
@@ -286,5 +286,5 @@ extern "C" int gf_hl_ransac(const float* kpts0, const float* kpts1, const int64_
         hl_rescore_kernel<<<dim3(B), dim3(256), 0, st>>>(w, M, L, ransac_th);
     }
     hl_final_kernel<<<dim3(B), dim3(256), 0, st>>>(w, M, L, H, inliers, line_inliers, num_inliers, success);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

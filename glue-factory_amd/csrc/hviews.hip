@@ -37,8 +37,7 @@
 // pw % 4 == 0 and `out` is 16-byte aligned; in the filter a wave owns whole 64-pixel rows (256-byte stores, conflict-free LDS
 // reads: 64 consecutive dwords) and the tile + the halo the view's taps really reach go through LDS.  Tap count, offsets and
 // weights are indexed by blockIdx and the loop counter only, so they stay wave-uniform (scalar loads).
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -215,8 +214,8 @@ extern "C" int gf_hv_warp(const void* src, int src_dtype, const int32_t* src_siz
     if (V > 65535 || (ph + TH - 1) / TH > 65535) return GF_ERR_SHAPE;
     if (src_dtype != GF_DTYPE_F32 && src_dtype != GF_DTYPE_U8) return GF_ERR_DTYPE;
     const dim3 grid((pw + TW - 1) / TW, (ph + TH - 1) / TH, V);
-    const int vec = (pw % 4 == 0) && ((uintptr_t)out % 16 == 0);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int vec = (pw % 4 == 0) && gf_aligned16(out);
+    hipStream_t st = gf_stream(stream);
 #define GF_HV_LAUNCH(T, CC) \
     hv_warp_kernel<T, CC><<<grid, 256, 0, st>>>((const T*)src, src_sizes, view_src, Hinv, params, out, S, Hmax, Wmax, ph, pw, \
                                                  finish != 0, gray != 0, vec)
@@ -226,7 +225,7 @@ extern "C" int gf_hv_warp(const void* src, int src_dtype, const int32_t* src_siz
         if (C == 1) GF_HV_LAUNCH(float, 1); else GF_HV_LAUNCH(float, 3);
     }
 #undef GF_HV_LAUNCH
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_hv_filter(const float* in, const int32_t* tap_off, const float* tap_w, const int32_t* ntaps, const float* params,
@@ -237,8 +236,8 @@ extern "C" int gf_hv_filter(const float* in, const int32_t* tap_off, const float
     if (Cout != (gray ? 1 : C)) return GF_ERR_SHAPE;
     if (V > 65535 || (ph + TH - 1) / TH > 65535) return GF_ERR_SHAPE;
     const dim3 grid((pw + TW - 1) / TW, (ph + TH - 1) / TH, V);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     if (C == 1) hv_filter_kernel<1><<<grid, 256, 0, st>>>(in, tap_off, tap_w, ntaps, params, out, ph, pw, gray != 0);
     else hv_filter_kernel<3><<<grid, 256, 0, st>>>(in, tap_off, tap_w, ntaps, params, out, ph, pw, gray != 0);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

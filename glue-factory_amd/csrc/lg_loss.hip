@@ -9,8 +9,7 @@
 // mixes the layers (a handful of [L,B] tensor ops for the whole step).
 // Backward: per-token gradients (dz, dt) are dense one-pass kernels; positives add their sparse terms
 // with atomics (any COO list is accepted, duplicates included).
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -214,23 +213,21 @@ extern "C" int gf_lg_loss_fwd(const void* md0, const void* md1, const float* z0,
     if (D <= 0 || D % 4) return GF_ERR_ALIGN;
     if (dtype != GF_F32 && dtype != GF_BF16) return GF_ERR_DTYPE;
     if ((t0 == nullptr) != (t1 == nullptr)) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     if (hipError_t e = gf_zero_f32(acc, (size_t)4 * B, st)) return (int)e;
     if (P > 0) {
         const dim3 grid((unsigned)((P + 4 * POS_CHUNK - 1) / (4 * POS_CHUNK)));
-        if (dtype == GF_BF16)
-            loss_pos_fwd_kernel<bf16_t><<<grid, dim3(256), 0, st>>>(
-                static_cast<const bf16_t*>(md0), static_cast<const bf16_t*>(md1), z0, z1, r, c, pos_b, pos_i, pos_j, P,
-                acc, M, N, D);
-        else
-            loss_pos_fwd_kernel<float><<<grid, dim3(256), 0, st>>>(
-                static_cast<const float*>(md0), static_cast<const float*>(md1), z0, z1, r, c, pos_b, pos_i, pos_j, P,
-                acc, M, N, D);
-        if (int e = (int)hipGetLastError()) return e;
+        const int e = gf_by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            loss_pos_fwd_kernel<T><<<grid, dim3(256), 0, st>>>(static_cast<const T*>(md0), static_cast<const T*>(md1), z0, z1, r, c,
+                                                              pos_b, pos_i, pos_j, P, acc, M, N, D);
+            return gf_launched();
+        });
+        if (e) return e;
     }
     loss_tok_fwd_kernel<<<dim3(2 * B), dim3(256), 0, st>>>(z0, z1, r, c, neg0, neg1, t0, t1, v0, a0, v1, a1, fin0, fin1,
                                                            tgt0, tgt1, acc, B, M, N);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_lg_loss_bwd_tokens(const float* z0, const float* z1, const float* neg0, const float* neg1,
@@ -239,14 +236,14 @@ extern "C" int gf_lg_loss_bwd_tokens(const float* z0, const float* z1, const flo
                                      const float* gacc, float* dz0, float* dz1, float* dt0, float* dt1,
                                      float* gr, float* gc, int B, int M, int N, void* stream) {
     if (B <= 0 || M <= 0 || N <= 0 || P < 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     loss_tok_bwd_kernel<<<dim3(2 * B), dim3(256), 0, st>>>(z0, z1, neg0, neg1, t0, t1, tgt0, tgt1, gacc, dz0, dz1, dt0,
                                                            dt1, gr, gc, B, M, N);
-    if (int e = (int)hipGetLastError()) return e;
+    if (int e = gf_launched()) return e;
     if (P > 0) {
         loss_pos_bwd_scalar_kernel<<<dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st>>>(
             z0, z1, pos_b, pos_i, pos_j, P, gacc, dz0, dz1, gr, gc, M, N);
-        if (int e = (int)hipGetLastError()) return e;
+        if (int e = gf_launched()) return e;
     }
     return 0;
 }
@@ -258,17 +255,12 @@ extern "C" int gf_lg_loss_bwd_rows(const void* md0, const void* md1,
     if (B <= 0 || M <= 0 || N <= 0 || P < 0) return GF_ERR_SHAPE;
     if (D <= 0 || D % 4) return GF_ERR_ALIGN;
     if (P == 0) return 0;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((P + 3) / 4));
-    if (dtype == GF_BF16)
-        loss_pos_bwd_rows_kernel<bf16_t><<<grid, dim3(256), 0, st>>>(
-            static_cast<const bf16_t*>(md0), static_cast<const bf16_t*>(md1), pos_b, pos_i, pos_j, P, gacc,
-            static_cast<bf16_t*>(dmd0), static_cast<bf16_t*>(dmd1), M, N, D);
-    else if (dtype == GF_F32)
-        loss_pos_bwd_rows_kernel<float><<<grid, dim3(256), 0, st>>>(
-            static_cast<const float*>(md0), static_cast<const float*>(md1), pos_b, pos_i, pos_j, P, gacc,
-            static_cast<float*>(dmd0), static_cast<float*>(dmd1), M, N, D);
-    else
-        return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        loss_pos_bwd_rows_kernel<T><<<grid, dim3(256), 0, gf_stream(stream)>>>(
+            static_cast<const T*>(md0), static_cast<const T*>(md1), pos_b, pos_i, pos_j, P, gacc, static_cast<T*>(dmd0),
+            static_cast<T*>(dmd1), M, N, D);
+        return gf_launched();
+    });
 }

@@ -12,8 +12,7 @@
 //                         log assignment; same argument roles as gf_assign_write)
 //   gf_dense_assign_bwd   d raw = G - exp(raw - r_i) A_i - exp(raw - c_j) B_j   (autograd of the above; A, B = the
 //                         gradient arriving at r and c, computed by the host from gf_dense_rowcol sums)
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -129,51 +128,50 @@ __global__ void dense_assign_bwd_kernel(const float* __restrict__ raw, const flo
 
 extern "C" int gf_rows_gather(const void* x, const int64_t* idx, void* out, int B, int E, int N, int D, int dtype, void* stream) {
     if (B <= 0 || E <= 0 || N <= 0 || D <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_F32) {
-        if (D % 4) return GF_ERR_ALIGN;
-        rows_gather_kernel<float><<<dim3(E, B), dim3(((D / 4 + 63) / 64) * 64), 0, st>>>(static_cast<const float*>(x), idx, static_cast<float*>(out), E, N, D);
-    } else if (dtype == GF_BF16) {
-        if (D % 8) return GF_ERR_ALIGN;
-        rows_gather_kernel<bf16_t><<<dim3(E, B), dim3(((D / 8 + 63) / 64) * 64), 0, st>>>(static_cast<const bf16_t*>(x), idx, static_cast<bf16_t*>(out), E, N, D);
-    } else return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        constexpr int VEC = Vec16<T>::N;
+        if (D % VEC) return GF_ERR_ALIGN;
+        rows_gather_kernel<T><<<dim3(E, B), dim3(((D / VEC + 63) / 64) * 64), 0, gf_stream(stream)>>>(
+            static_cast<const T*>(x), idx, static_cast<T*>(out), E, N, D);
+        return gf_launched();
+    });
 }
 
 extern "C" int gf_line_pair_scores(const float* S, const float* draw, float* out, int B, int M, int N, int backward, void* stream) {
     if (B <= 0 || M <= 0 || N <= 0) return GF_ERR_SHAPE;
     if (M > 65535 || B > 65535) return GF_ERR_UNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     const dim3 grid((N + 255) / 256, M, B);
     if (backward) pair_scores_bwd_kernel<<<grid, dim3(256), 0, st>>>(S, draw, out, M, N);
     else pair_scores_fwd_kernel<<<grid, dim3(256), 0, st>>>(S, out, M, N);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_dense_rowcol(const float* z, int64_t batch_stride, int64_t ld, float* rows, float* cols, int B, int M, int N,
                                int mode, void* stream) {
     if (B <= 0 || M <= 0 || N <= 0) return GF_ERR_SHAPE;
     if (B > 65535) return GF_ERR_UNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     if (rows) dense_rows_kernel<<<dim3((M + 3) / 4, B), dim3(256), 0, st>>>(z, batch_stride, ld, rows, M, N, mode);
     if (cols) dense_cols_kernel<<<dim3((N + 63) / 64, B), dim3(256), 0, st>>>(z, batch_stride, ld, cols, M, N, mode);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_dense_assign(const float* raw, const float* row_bias, const float* col_bias, const float* bin_row,
                                const float* bin_col, float corner, float* out, int B, int M, int N, void* stream) {
     if (B <= 0 || M <= 0 || N <= 0) return GF_ERR_SHAPE;
     if (M + 1 > 65535 || B > 65535) return GF_ERR_UNSUPPORTED;
-    dense_assign_kernel<<<dim3((N + 256) / 256, M + 1, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    dense_assign_kernel<<<dim3((N + 256) / 256, M + 1, B), dim3(256), 0, gf_stream(stream)>>>(
         raw, row_bias, col_bias, bin_row, bin_col, corner, out, M, N);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_dense_assign_bwd(const float* raw, const float* r, const float* c, const float* A, const float* Bv,
                                    const float* G, float* draw, int B, int M, int N, void* stream) {
     if (B <= 0 || M <= 0 || N <= 0) return GF_ERR_SHAPE;
     if (M > 65535 || B > 65535) return GF_ERR_UNSUPPORTED;
-    dense_assign_bwd_kernel<<<dim3((N + 255) / 256, M, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    dense_assign_bwd_kernel<<<dim3((N + 255) / 256, M, B), dim3(256), 0, gf_stream(stream)>>>(
         raw, r, c, A, Bv, G, draw, M, N);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

@@ -11,8 +11,7 @@
 //                residual add is fused) and the backward of the gather (s0 = d msg[:, :D], s1 = d msg[:, D:2D]);
 //   line_expand  d upd[e] = scale_{idx[e]} * g[idx[e]]          (backward of the aggregation)
 // All are O(E D) streaming kernels on [B, E <= 4096, D] tensors; T = float or bf16 (fp32 accumulation).
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -111,52 +110,44 @@ extern "C" int gf_line_csr(const int64_t* idx, int* order, int* seg, int B, int 
     if (B <= 0 || E <= 0 || N <= 0) return GF_ERR_SHAPE;
     if (E > 4096 || N > 8192 || (E & 1)) return GF_ERR_UNSUPPORTED;
     const size_t lds = (size_t)(E + N + 1) * 4;
-    line_csr_kernel<<<dim3(B), 256, lds, reinterpret_cast<hipStream_t>(stream)>>>(idx, order, seg, E, N);
-    return (int)hipGetLastError();
+    line_csr_kernel<<<dim3(B), 256, lds, gf_stream(stream)>>>(idx, order, seg, E, N);
+    return gf_launched();
 }
 
 extern "C" int gf_line_gather(const void* x, const int64_t* idx, const void* enc, void* msg, int B, int E, int N, int D,
                               int dtype, void* stream) {
     if (B <= 0 || E <= 0 || N <= 0 || D <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_BF16) {
-        if (D % 8 || D > 8 * 1024) return GF_ERR_UNSUPPORTED;
-        line_gather_kernel<bf16_t><<<dim3(E, B), D / 8, 0, st>>>(static_cast<const bf16_t*>(x), idx, static_cast<const bf16_t*>(enc),
-                                                               static_cast<bf16_t*>(msg), E, N, D);
-    } else if (dtype == GF_F32) {
-        if (D % 4 || D > 4 * 1024) return GF_ERR_UNSUPPORTED;
-        line_gather_kernel<float><<<dim3(E, B), D / 4, 0, st>>>(static_cast<const float*>(x), idx, static_cast<const float*>(enc),
-                                                              static_cast<float*>(msg), E, N, D);
-    } else return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        constexpr int VEC = Vec16<T>::N;
+        if (D % VEC || D > VEC * 1024) return GF_ERR_UNSUPPORTED;
+        line_gather_kernel<T><<<dim3(E, B), D / VEC, 0, gf_stream(stream)>>>(
+            static_cast<const T*>(x), idx, static_cast<const T*>(enc), static_cast<T*>(msg), E, N, D);
+        return gf_launched();
+    });
 }
 
 extern "C" int gf_line_segsum(const void* s0, int64_t ld0, const void* s1, int64_t ld1, const int* order, const int* seg,
                               const void* base, void* out, int B, int E, int N, int D, int mode, int dtype, void* stream) {
     if (B <= 0 || E <= 0 || N <= 0 || D <= 0) return GF_ERR_SHAPE;
     if (D % 4 || D > 4096 || ld0 % 4 || (s1 && ld1 % 4)) return GF_ERR_UNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_BF16)
-        line_segsum_kernel<bf16_t><<<dim3(N, B), D / 4, 0, st>>>(static_cast<const bf16_t*>(s0), ld0, static_cast<const bf16_t*>(s1), ld1,
-                                                               order, seg, static_cast<const bf16_t*>(base),
-                                                               static_cast<bf16_t*>(out), E, N, D, mode);
-    else if (dtype == GF_F32)
-        line_segsum_kernel<float><<<dim3(N, B), D / 4, 0, st>>>(static_cast<const float*>(s0), ld0, static_cast<const float*>(s1), ld1,
-                                                              order, seg, static_cast<const float*>(base),
-                                                              static_cast<float*>(out), E, N, D, mode);
-    else return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        line_segsum_kernel<T><<<dim3(N, B), D / 4, 0, gf_stream(stream)>>>(
+            static_cast<const T*>(s0), ld0, static_cast<const T*>(s1), ld1, order, seg, static_cast<const T*>(base),
+            static_cast<T*>(out), E, N, D, mode);
+        return gf_launched();
+    });
 }
 
 extern "C" int gf_line_expand(const void* g, const int64_t* idx, const int* seg, void* d, int B, int E, int N, int D,
                               int mode, int dtype, void* stream) {
     if (B <= 0 || E <= 0 || N <= 0 || D <= 0) return GF_ERR_SHAPE;
     if (D % 4 || D > 4096) return GF_ERR_UNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_BF16)
-        line_expand_kernel<bf16_t><<<dim3(E, B), D / 4, 0, st>>>(static_cast<const bf16_t*>(g), idx, seg, static_cast<bf16_t*>(d), E, N, D, mode);
-    else if (dtype == GF_F32)
-        line_expand_kernel<float><<<dim3(E, B), D / 4, 0, st>>>(static_cast<const float*>(g), idx, seg, static_cast<float*>(d), E, N, D, mode);
-    else return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        line_expand_kernel<T><<<dim3(E, B), D / 4, 0, gf_stream(stream)>>>(static_cast<const T*>(g), idx, seg, static_cast<T*>(d),
+                                                                        E, N, D, mode);
+        return gf_launched();
+    });
 }

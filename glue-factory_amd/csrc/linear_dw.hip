@@ -23,8 +23,7 @@
 // staging is unguarded, 128 columns wide and bf16-only, so ragged shapes and fp32 need them.
 #include <cstdlib>
 #include <type_traits>
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 #ifndef GF_DW_WG          // workgroup slots of one dW round (two per CU); probe builds override it
 #define GF_DW_WG 512
@@ -649,7 +648,7 @@ enum DwTier { DW_F32, DW_TR, DW_DMA };
 int select_kernel(int dtype, int Nout, int K, bool two_source) {
     const bool dma = dtype == GF_BF16 && Nout % 128 == 0 && K % 128 == 0;
     if (two_source) return dma ? DW_DMA : GF_ERR_UNSUPPORTED;     // only the DMA tier picks its X source per k-tile
-    const int align = dtype == GF_BF16 ? 8 : 4;                   // 16-byte rows
+    const int align = gf_vec_elems(dtype);                        // 16-byte rows
     if (Nout % align || K % align) return GF_ERR_ALIGN;
     if (dtype == GF_F32) return DW_F32;
     if (dtype != GF_BF16) return GF_ERR_DTYPE;
@@ -658,10 +657,8 @@ int select_kernel(int dtype, int Nout, int K, bool two_source) {
 
 // Every tier asks for 64 KiB of dynamic LDS or more (64, 80 and 136 KiB).  The limit without this call is not 48 KiB:
 // gf_ln_gelu_bwd at bf16 C = 2048 launches with exactly 65536 bytes and no attribute (tests/test_gpu_elementwise.py,
-// test_ln_gelu[bfloat16-2048]).  Nothing above 64 KiB has been launched without the opt-in, so all three keep it.
-hipError_t allow_lds(const void* kernel, int bytes) {
-    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
+// test_ln_gelu[bfloat16-2048]).  Nothing above 64 KiB has been launched without the opt-in, so all three keep it
+// (gf_allow_lds in launch()).
 
 // plan -> carve the workspace -> tile kernel of `tier` -> slice reduction.  x2 / K1: the second source (DMA tier) or null / 0.
 int launch(DwTier tier, const void* dy, const void* x, const void* x2, int K1, float* dw, float* db, void* ws,
@@ -672,27 +669,26 @@ int launch(DwTier tier, const void* dy, const void* x, const void* x2, int K1, f
     float* bpart = part + p.nslice * nw;                          // [nslice][Nout]
     const dim3 grid(p.ntile * ((p.nslice + 7) / 8) * 8);          // slices padded to the 8 XCDs dw_tile() deals them to
     const bf16_t *dyh = reinterpret_cast<const bf16_t*>(dy), *xh = reinterpret_cast<const bf16_t*>(x);
-    hipError_t e;
     switch (tier) {
     case DW_F32:
-        if ((e = allow_lds(reinterpret_cast<const void*>(linear_dw_f32_kernel), F32_LDS)) != hipSuccess) return (int)e;
+        if (int e = gf_allow_lds(linear_dw_f32_kernel, F32_LDS)) return e;
         linear_dw_f32_kernel<<<grid, 256, F32_LDS, st>>>(reinterpret_cast<const float*>(dy), reinterpret_cast<const float*>(x),
                                                          part, bpart, M, Nout, K, p.rows);
         break;
     case DW_TR:
-        if ((e = allow_lds(reinterpret_cast<const void*>(linear_dw_tr_kernel), TR_LDS)) != hipSuccess) return (int)e;
+        if (int e = gf_allow_lds(linear_dw_tr_kernel, TR_LDS)) return e;
         linear_dw_tr_kernel<<<grid, 256, TR_LDS, st>>>(dyh, xh, part, bpart, M, Nout, K, p.rows);
         break;
     case DW_DMA:
-        if ((e = allow_lds(reinterpret_cast<const void*>(linear_dw_dma_kernel), DM_LDS)) != hipSuccess) return (int)e;
+        if (int e = gf_allow_lds(linear_dw_dma_kernel, DM_LDS)) return e;
         linear_dw_dma_kernel<<<grid, 256, DM_LDS, st>>>(dyh, xh, reinterpret_cast<const bf16_t*>(x2), K1, part, bpart, M, Nout, K,
                                                         p.rows);
         break;
     }
-    if (int rc = (int)hipGetLastError()) return rc;
+    if (int rc = gf_launched()) return rc;
     const int nwb = (int)((nw / 4 + 63) / 64), nbb = db ? (Nout / 4 + 63) / 64 : 0;   // 64 float4 columns per block
     linear_dw_reduce<<<dim3(nwb + nbb), 256, 0, st>>>(part, bpart, dw, db, p.nslice, nw, Nout, nwb);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 }  // namespace
@@ -709,7 +705,7 @@ extern "C" int gf_linear_dw2(const void* dy, const void* x1, const void* x2, int
     if (K1 % 128 || x1 == nullptr || x2 == nullptr) return GF_ERR_UNSUPPORTED;      // a k-tile reads ONE source
     const int tier = select_kernel(dtype, Nout, K, true);
     if (tier < 0) return tier;
-    return launch((DwTier)tier, dy, x1, x2, K1, dw, db, ws, M, Nout, K, reinterpret_cast<hipStream_t>(stream));
+    return launch((DwTier)tier, dy, x1, x2, K1, dw, db, ws, M, Nout, K, gf_stream(stream));
 }
 
 extern "C" int gf_linear_dw(const void* dy, const void* x, float* dw, float* db, void* ws,
@@ -717,5 +713,5 @@ extern "C" int gf_linear_dw(const void* dy, const void* x, float* dw, float* db,
     if (M <= 0 || Nout <= 0 || K <= 0) return GF_ERR_SHAPE;
     const int tier = select_kernel(dtype, Nout, K, false);
     if (tier < 0) return tier;
-    return launch((DwTier)tier, dy, x, nullptr, 0, dw, db, ws, M, Nout, K, reinterpret_cast<hipStream_t>(stream));
+    return launch((DwTier)tier, dy, x, nullptr, 0, dw, db, ws, M, Nout, K, gf_stream(stream));
 }

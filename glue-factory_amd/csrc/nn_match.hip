@@ -7,6 +7,7 @@
 // gf_rows_top2 uses the skeleton of assignment.hip (assign_common.h): the owner rows' fragments stay in registers, the
 // other matrix streams through LDS in 64-row MFMA tiles, and the running (best, arg, second) of a row is lane-local until
 // the two half waves meet once at the end.  The N-pair kernels are dense element-wise passes with reductions: no MFMA.
+#include "gf_launch.h"
 #include "gf_common.h"
 #include "assign_common.h"
 #include "gf_amd.h"
@@ -85,7 +86,7 @@ template <typename T, int D> int launch_top2_td(const HeadParams& p, hipStream_t
     const size_t lds = head_lds<T, D>();
     if (int e = set_lds(rows_top2_kernel<T, D>, lds)) return e;
     rows_top2_kernel<T, D><<<dim3(total), dim3(256), lds, st>>>(p);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 template <typename T> int launch_top2_t(const HeadParams& p, int D, hipStream_t st) {
@@ -256,10 +257,7 @@ extern "C" int gf_rows_top2(const void* a, const void* b, float* best, int64_t* 
     if (best == nullptr || arg == nullptr || second == nullptr) return GF_ERR_SHAPE;
     HeadParams p = {};
     p.own = a; p.oth = b; p.B = B; p.No = M; p.Ns = N; p.f0 = best; p.i0 = arg; p.f1 = second;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == GF_F32) return launch_top2_t<float>(p, D, st);
-    if (dtype == GF_BF16) return launch_top2_t<bf16_t>(p, D, st);
-    return GF_ERR_DTYPE;
+    return gf_by_dtype(dtype, [&](auto t) { return launch_top2_t<decltype(t)>(p, D, gf_stream(stream)); });
 }
 
 extern "C" int gf_nn_filter(const float* best0, const int64_t* arg0, const float* second0,
@@ -269,9 +267,9 @@ extern "C" int gf_nn_filter(const float* best0, const int64_t* arg0, const float
     if (B <= 0 || M <= 0 || N <= 0) return GF_ERR_SHAPE;
     const int64_t tot = (int64_t)B * (M + N);
     if (tot >= ((int64_t)1 << 31)) return GF_ERR_UNSUPPORTED;
-    nn_filter_kernel<<<dim3(blocks_for(tot, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    nn_filter_kernel<<<dim3(blocks_for(tot, 256)), dim3(256), 0, gf_stream(stream)>>>(
         best0, arg0, second0, best1, arg1, second1, ratio2, dist2, mutual, m0, m1, s0, s1, B, M, N);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_npair_fwd(const float* sim, const float* temperature, const int64_t* pb, const int64_t* pi,
@@ -279,7 +277,7 @@ extern "C" int gf_npair_fwd(const float* sim, const float* temperature, const in
                             float* cnt_row, float* cnt_col, int B, int M, int N, void* stream) {
     if (B <= 0 || M <= 0 || N <= 0 || P < 0) return GF_ERR_SHAPE;
     if ((int64_t)B * M * N >= ((int64_t)1 << 31)) return GF_ERR_UNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     if (hipError_t e = gf_zero_f32(acc, (size_t)B, st)) return (int)e;
     if (hipError_t e = gf_zero_f32(cnt, (size_t)B, st)) return (int)e;
     if (hipError_t e = gf_zero_f32(cnt_row, (size_t)B * M, st)) return (int)e;
@@ -290,7 +288,7 @@ extern "C" int gf_npair_fwd(const float* sim, const float* temperature, const in
     if (P > 0)
         npair_pos_kernel<<<dim3(blocks_for(P, 256)), dim3(256), 0, st>>>(sim, temperature, lse_row, lse_col, pb, pi, pj, P,
                                                                          acc, cnt, cnt_row, cnt_col, B, M, N);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_npair_bwd(const float* sim, const float* temperature, const float* lse_row, const float* lse_col,
@@ -300,12 +298,12 @@ extern "C" int gf_npair_bwd(const float* sim, const float* temperature, const fl
     if (B <= 0 || M <= 0 || N <= 0 || P < 0) return GF_ERR_SHAPE;
     const int64_t tot = (int64_t)B * M * N;
     if (tot >= ((int64_t)1 << 31)) return GF_ERR_UNSUPPORTED;      // one thread per element of the dense similarity
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     if (hipError_t e = gf_zero_f32(dT, 1, st)) return (int)e;
     npair_bwd_dense_kernel<<<dim3(blocks_for(tot, 256)), dim3(256), 0, st>>>(sim, temperature, lse_row, lse_col, cnt_row,
                                                                              cnt_col, coef, dsim, dT, B, M, N);
     if (P > 0)
         npair_bwd_pos_kernel<<<dim3(blocks_for(P, 256)), dim3(256), 0, st>>>(sim, temperature, coef, pb, pi, pj, P, dsim, dT,
                                                                              B, M, N);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

@@ -24,8 +24,7 @@
 // Jacobi sweeps on the 9 x 9 matrix in LDS (gf_jacobi9.h), the eigenvector of the smallest eigenvalue, de-normalisation on
 // the view-0 side.
 #pragma once
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 #include "gf_jacobi9.h"
 
 namespace {
@@ -92,7 +91,7 @@ inline void carve_lines(Carver& c, int B, int L, LineWs& w) {
 inline int ws_check(int B, const void* ws, int64_t ws_bytes, int64_t nblk, int64_t lanes, size_t need) {
     if ((int64_t)B * nblk >= ((int64_t)1 << 31) || (int64_t)B * lanes >= ((int64_t)1 << 31)) return GF_ERR_UNSUPPORTED;
     if (ws_bytes < (int64_t)need) return GF_ERR_SHAPE;
-    if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) return GF_ERR_ALIGN;
+    if (!gf_aligned16(ws)) return GF_ERR_ALIGN;
     return 0;
 }
 

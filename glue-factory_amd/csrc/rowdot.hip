@@ -4,8 +4,7 @@
 //   fwd    one wave per row, 16-byte loads, butterfly reduction            (reads x once)
 //   bwd    dx[m,:] = dz[m] * w (optional, elementwise)                     (writes dx once)
 //          dw = sum_m dz[m] x[m,:], db = sum_m dz[m] via per-block column partials (reads x once)
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -178,68 +177,56 @@ extern "C" int gf_rowdot_nblk(int M) { return rd_blocks(M); }
 extern "C" int gf_rowdot_fwd(const void* x, const float* w, float bias, const float* bias_dev, float* z, int M, int C,
                              int dtype, void* stream) {
     if (M <= 0 || C <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int nb = (int)(((int64_t)M + 3) / 4 > 4096 ? 4096 : ((int64_t)M + 3) / 4);
-    if (dtype == GF_F32) {
-        if (int e = rd_check<float>(C)) return e;
-        rowdot_fwd_kernel<float><<<nb, 256, 0, st>>>(reinterpret_cast<const float*>(x), w, bias, bias_dev, z, M, C);
-    } else if (dtype == GF_BF16) {
-        if (int e = rd_check<bf16_t>(C)) return e;
-        rowdot_fwd_kernel<bf16_t><<<nb, 256, 0, st>>>(reinterpret_cast<const bf16_t*>(x), w, bias, bias_dev, z, M, C);
-    } else return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (int e = rd_check<T>(C)) return e;
+        rowdot_fwd_kernel<T><<<nb, 256, 0, gf_stream(stream)>>>(reinterpret_cast<const T*>(x), w, bias, bias_dev, z, M, C);
+        return gf_launched();
+    });
 }
 
 extern "C" int gf_rowdot_bwd(const void* x, const float* dz, const float* w, void* dx, const void* base, float* part,
                              int M, int C, int dtype, void* stream) {
     if (M <= 0 || C <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nb = rd_blocks(M);
-    if (dtype == GF_F32) {
-        if (int e = rd_check<float>(C)) return e;
-        size_t lds = 256 * 5 * sizeof(float);
-        if (dx) rowdot_bwd_kernel<float, true><<<nb, 256, lds, st>>>(reinterpret_cast<const float*>(x), dz, w, reinterpret_cast<float*>(dx), reinterpret_cast<const float*>(base), part, M, C);
-        else rowdot_bwd_kernel<float, false><<<nb, 256, lds, st>>>(reinterpret_cast<const float*>(x), dz, w, nullptr, nullptr, part, M, C);
-    } else if (dtype == GF_BF16) {
-        if (int e = rd_check<bf16_t>(C)) return e;
-        size_t lds = 256 * 9 * sizeof(float);
-        if (dx) rowdot_bwd_kernel<bf16_t, true><<<nb, 256, lds, st>>>(reinterpret_cast<const bf16_t*>(x), dz, w, reinterpret_cast<bf16_t*>(dx), reinterpret_cast<const bf16_t*>(base), part, M, C);
-        else rowdot_bwd_kernel<bf16_t, false><<<nb, 256, lds, st>>>(reinterpret_cast<const bf16_t*>(x), dz, w, nullptr, nullptr, part, M, C);
-    } else return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (int e = rd_check<T>(C)) return e;
+        const size_t lds = 256 * (Vec16<T>::N + 1) * sizeof(float);
+        return gf_by_bool(dx != nullptr, [&](auto has_dx) {
+            rowdot_bwd_kernel<T, decltype(has_dx)::value><<<nb, 256, lds, gf_stream(stream)>>>(
+                reinterpret_cast<const T*>(x), dz, w, reinterpret_cast<T*>(dx), reinterpret_cast<const T*>(base), part, M, C);
+            return gf_launched();
+        });
+    });
 }
 
 
 extern "C" int gf_rowdot2_fwd(const void* x, const float* w0, const float* w1, const float* b0, const float* b1, float* z0,
                               float* z1, int M, int C, int dtype, void* stream) {
     if (M <= 0 || C <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int nb = (int)(((int64_t)M + 3) / 4 > 4096 ? 4096 : ((int64_t)M + 3) / 4);
-    if (dtype == GF_F32) {
-        if (int e = rd_check<float>(C)) return e;
-        rowdot2_fwd_kernel<float><<<nb, 256, 0, st>>>(reinterpret_cast<const float*>(x), w0, w1, b0, b1, z0, z1, M, C);
-    } else if (dtype == GF_BF16) {
-        if (int e = rd_check<bf16_t>(C)) return e;
-        rowdot2_fwd_kernel<bf16_t><<<nb, 256, 0, st>>>(reinterpret_cast<const bf16_t*>(x), w0, w1, b0, b1, z0, z1, M, C);
-    } else return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (int e = rd_check<T>(C)) return e;
+        rowdot2_fwd_kernel<T><<<nb, 256, 0, gf_stream(stream)>>>(reinterpret_cast<const T*>(x), w0, w1, b0, b1, z0, z1, M, C);
+        return gf_launched();
+    });
 }
 
 extern "C" int gf_rowdot2_bwd(const void* x, const float* dz0, const float* dz1, const float* w0, void* dx, const void* base,
                               float* part, int M, int C, int dtype, void* stream) {
     if (M <= 0 || C <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nb = rd_blocks(M);
-    if (dtype == GF_F32) {
-        if (int e = rd_check<float>(C)) return e;
-        size_t lds = 256 * 10 * sizeof(float);
-        if (dx) rowdot2_bwd_kernel<float, true><<<nb, 256, lds, st>>>(reinterpret_cast<const float*>(x), dz0, dz1, w0, reinterpret_cast<float*>(dx), reinterpret_cast<const float*>(base), part, M, C);
-        else rowdot2_bwd_kernel<float, false><<<nb, 256, lds, st>>>(reinterpret_cast<const float*>(x), dz0, dz1, w0, nullptr, nullptr, part, M, C);
-    } else if (dtype == GF_BF16) {
-        if (int e = rd_check<bf16_t>(C)) return e;
-        size_t lds = 256 * 18 * sizeof(float);
-        if (dx) rowdot2_bwd_kernel<bf16_t, true><<<nb, 256, lds, st>>>(reinterpret_cast<const bf16_t*>(x), dz0, dz1, w0, reinterpret_cast<bf16_t*>(dx), reinterpret_cast<const bf16_t*>(base), part, M, C);
-        else rowdot2_bwd_kernel<bf16_t, false><<<nb, 256, lds, st>>>(reinterpret_cast<const bf16_t*>(x), dz0, dz1, w0, nullptr, nullptr, part, M, C);
-    } else return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (int e = rd_check<T>(C)) return e;
+        const size_t lds = 256 * 2 * (Vec16<T>::N + 1) * sizeof(float);
+        return gf_by_bool(dx != nullptr, [&](auto has_dx) {
+            rowdot2_bwd_kernel<T, decltype(has_dx)::value><<<nb, 256, lds, gf_stream(stream)>>>(
+                reinterpret_cast<const T*>(x), dz0, dz1, w0, reinterpret_cast<T*>(dx), reinterpret_cast<const T*>(base), part, M, C);
+            return gf_launched();
+        });
+    });
 }

@@ -126,8 +126,8 @@ extern "C" int gf_sinkhorn_fwd(const float* Z, float* out, float* u_hist, float*
     if (B <= 0 || M <= 0 || N <= 0 || iters < 0 || (schedule & 3) == 3) return GF_ERR_SHAPE;
     const Geo g = make_geo(B, M, N);
     if (g.RB < 1) return GF_ERR_UNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(ws) & 15) return GF_ERR_ALIGN;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (!gf_aligned16(ws)) return GF_ERR_ALIGN;
+    hipStream_t st = gf_stream(stream);
     const Ws w = carve(ws, g, iters);
     const Choice c = select_tier(g, B, iters, false, schedule, 0, w);
     SkrArgs ra{};
@@ -164,7 +164,7 @@ extern "C" int gf_sinkhorn_fwd(const float* Z, float* out, float* u_hist, float*
             sk_final_fwd_launch(Zc, iters ? uh + (size_t)(iters - 1) * B * g.R : nullptr,
                                 iters ? vh + (size_t)(iters - 1) * B * g.C : nullptr, out + b0 * zs, g, bc, st);
     }
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_sinkhorn_bwd(const float* Z, const float* gout, const float* gsum_row, const float* gsum_col,
@@ -173,8 +173,8 @@ extern "C" int gf_sinkhorn_bwd(const float* Z, const float* gout, const float* g
     if (B <= 0 || M <= 0 || N <= 0 || iters < 0 || (schedule & 3) == 3) return GF_ERR_SHAPE;
     const Geo g = make_geo(B, M, N);
     if (g.RB < 1) return GF_ERR_UNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(ws) & 15) return GF_ERR_ALIGN;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (!gf_aligned16(ws)) return GF_ERR_ALIGN;
+    hipStream_t st = gf_stream(stream);
     const Ws w = carve(ws, g, iters);             // ubar_hist [iters, B, R] (index k-1), vbar_hist [iters+1, B, C] (index k = 0..T)
     const size_t zs = (size_t)g.R * g.C;
     if (iters == 0) return (int)gf_copy_f32(gZ, gout, (size_t)B * zs, st);
@@ -218,5 +218,5 @@ extern "C" int gf_sinkhorn_bwd(const float* Z, const float* gout, const float* g
         if (rc) return rc;
         skf_final_bwd_launch(Zc, gout + b0 * zs, uh, vh, ubh, vbh, w.P, w.Q, w.KP, gZ + b0 * zs, g, bc, iters, st);
     }
-    return (int)hipGetLastError();
+    return gf_launched();
 }

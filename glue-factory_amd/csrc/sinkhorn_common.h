@@ -24,8 +24,7 @@
 // resident plan and the launch functions sinkhorn.hip dispatches to.  Everything is in a named namespace or inline so that
 // every unit can include it; the kernels themselves stay in their unit's anonymous namespace.
 #pragma once
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace gfsk {
 

@@ -245,15 +245,13 @@ namespace gfsk {
 int sk_fwd_launch(const float* Z, float* ucur, float* vcur, float* u_hist, float* v_hist, float* pm, float* ps, const Geo& g,
                   int bc, int iters, hipStream_t st) {
     const size_t lds = rows_lds(g, false);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sk_rows_fwd),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
+    if (int e = gf_allow_lds(sk_rows_fwd, lds)) return e;
     for (int it = 0; it < iters; ++it) {
         sk_rows_fwd<<<dim3(g.nblk, bc), SK_THREADS, lds, st>>>(Z, it == 0 ? nullptr : vcur, ucur,
                                                                u_hist + (size_t)it * g.B * g.R, pm, ps, g);
         sk_cols_fwd<<<dim3((g.C + 63) / 64, bc), 256, 0, st>>>(pm, ps, vcur, v_hist + (size_t)it * g.B * g.C, g);
     }
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 // u, v: the iterates to add (natural-log units), or null for zero
@@ -265,9 +263,7 @@ void sk_final_fwd_launch(const float* Z, const float* u, const float* v, float* 
 int sk_bwd_launch(const float* Z, const float* G, const float* gsum_row, const float* u_hist, const float* v_hist,
                   float* ubar_hist, float* vbar_hist, float* psum, float* gZ, const Geo& g, int bc, int iters, hipStream_t st) {
     const size_t lds = rows_lds(g, true);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sk_rows_bwd),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
+    if (int e = gf_allow_lds(sk_rows_bwd, lds)) return e;
     const size_t us = (size_t)g.B * g.R, vs = (size_t)g.B * g.C;
     for (int k = iters; k >= 1; --k) {
         sk_rows_bwd<<<dim3(g.nblk, bc), SK_THREADS, lds, st>>>(
@@ -277,7 +273,7 @@ int sk_bwd_launch(const float* Z, const float* G, const float* gsum_row, const f
     }
     sk_final_bwd<<<dim3((g.C + 255) / 256, (g.R + 7) / 8, bc), 256, 0, st>>>(Z, G, u_hist, v_hist, ubar_hist, vbar_hist + vs, gZ,
                                                                              iters, us, vs, us, vs, g);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 }  // namespace gfsk

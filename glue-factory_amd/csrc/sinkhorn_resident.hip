@@ -563,9 +563,7 @@ template <bool BWD> static int skr_launch(const SkrArgs& a, hipStream_t st) {
     const dim3 grid((unsigned)(a.d.wpp * a.d.bc));
 #define SKR_CASE(NSM_)                                                                                                 \
     case NSM_: {                                                                                                       \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(skr_kernel<NSM_, BWD>),                       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.d.lds);                  \
-        if (e != hipSuccess) return (int)e;                                                                            \
+        if (int e = gf_allow_lds(skr_kernel<NSM_, BWD>, a.d.lds)) return e;                                            \
         skr_kernel<NSM_, BWD><<<grid, 256, a.d.lds, st>>>(a);                                                          \
         break;                                                                                                         \
     }
@@ -574,7 +572,7 @@ template <bool BWD> static int skr_launch(const SkrArgs& a, hipStream_t st) {
         default: return GF_ERR_UNSUPPORTED;
     }
 #undef SKR_CASE
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 int skr_fwd_launch(const SkrArgs& a, hipStream_t st) { return skr_launch<false>(a, st); }

@@ -376,7 +376,7 @@ template <int NS> int skf_fwd_iters(const float* Zp, float* v2, float* u2, float
         else skf_fwd_iter<NS, false><<<dim3(g.nblk, bc), 256, 0, st>>>(Zp, v2, u2, uh, part, g);
         skf_cols_fwd<<<dim3((g.Cp + 63) / 64, bc), 256, 0, st>>>(part, v2, v_hist + (size_t)it * g.B * g.C, it == 0, g);
     }
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 // a2p / vbp: as skf_bwd_prep left them for k = T
 template <int NS> int skf_bwd_iters(const float* Zp, const float* u_hist, const float* v_hist, const float* gsum_row,
@@ -391,7 +391,7 @@ template <int NS> int skf_bwd_iters(const float* Zp, const float* u_hist, const 
         skf_cols_bwd<<<dim3((g.Cp + 63) / 64, bc), 256, 0, st>>>(part, vk, vp, vbar_hist + (size_t)(k - 1) * g.B * g.C,
                                                                  a2p, vbp, g);
     }
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 // index of the NS instantiation that holds a row of g (make_geo: g.fast <=> at most SKF_MAX_NS * 64 float4 per row)

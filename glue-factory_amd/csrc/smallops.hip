@@ -11,8 +11,7 @@
 //   gf_small_dw              dW[o, k] = sum_m dy[m, o] x[m, k] for a tall dy [M, O] and a FEW input columns (K <= 8):
 //                            the gradient of the Fourier positional encoding's Wr (lightglue.py:52-65; M = 131072,
 //                            O = 32, K = 2), which the library ran as a 0.4 ms skinny GEMM.
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -178,12 +177,11 @@ __global__ void small_dw_stage2(const float* __restrict__ part, float* __restric
 
 extern "C" int gf_multi_cast_transpose(const void* table, int n_entries, int total_tiles, int dtype, void* stream) {
     if (n_entries <= 0 || total_tiles <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const CastEntry* tab = static_cast<const CastEntry*>(table);
-    if (dtype == GF_BF16) multi_cast_transpose_kernel<bf16_t><<<dim3(total_tiles), dim3(256), 0, st>>>(tab, n_entries);
-    else if (dtype == GF_F32) multi_cast_transpose_kernel<float><<<dim3(total_tiles), dim3(256), 0, st>>>(tab, n_entries);
-    else return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        multi_cast_transpose_kernel<decltype(t)><<<dim3(total_tiles), dim3(256), 0, gf_stream(stream)>>>(tab, n_entries);
+        return gf_launched();
+    });
 }
 extern "C" int gf_cast_entry_bytes(void) { return (int)sizeof(CastEntry); }
 
@@ -192,24 +190,24 @@ extern "C" int gf_weight_grad_map(const float* g, float* out, const int* perm, c
     if (rows <= 0 || cols <= 0) return GF_ERR_SHAPE;
     const size_t total = (size_t)rows * cols;
     const int nb = (int)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
-    weight_grad_map_kernel<<<dim3(nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(g, out, perm, cperm, rscale, scale, rows, cols);
-    return (int)hipGetLastError();
+    weight_grad_map_kernel<<<dim3(nb), dim3(256), 0, gf_stream(stream)>>>(g, out, perm, cperm, rscale, scale, rows, cols);
+    return gf_launched();
 }
 
 extern "C" int gf_colsum_f32(const float* x, float* ws, float* out, int G, int R, int C, void* stream) {
     if (G <= 0 || R <= 0 || C <= 0) return GF_ERR_SHAPE;
     if (G > 65535) return GF_ERR_UNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     colsum_stage1<<<dim3((C + 63) / 64, CS_CHUNKS, G), dim3(256), 0, st>>>(x, ws, R, C);
     colsum_stage2<<<dim3((C + 255) / 256, G), dim3(256), 0, st>>>(ws, out, C);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 extern "C" int gf_colsum_ws_floats(int G, int C) { return G * CS_CHUNKS * C; }
 
 extern "C" int gf_small_dw(const float* dy, const float* x, float* ws, float* dw, int M, int O, int K, void* stream) {
     if (M <= 0 || O <= 0 || K <= 0) return GF_ERR_SHAPE;
     if (O > 256 || K > 8 || O * K > 256) return GF_ERR_UNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     const size_t lds = (size_t)(256 / O) * O * K * sizeof(float);
 #define GF_SDW(K_) case K_: small_dw_stage1<K_><<<dim3(SDW_BLOCKS), dim3(256), lds, st>>>(dy, x, ws, M, O); break;
     switch (K) {
@@ -218,14 +216,14 @@ extern "C" int gf_small_dw(const float* dy, const float* x, float* ws, float* dw
     }
 #undef GF_SDW
     small_dw_stage2<<<dim3((O * K + 255) / 256), dim3(256), 0, st>>>(ws, dw, O * K);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 extern "C" int gf_small_dw_ws_floats(int O, int K) { return SDW_BLOCKS * O * K; }
 
 extern "C" int gf_small_fwd(const float* x, const float* w, float* y, int M, int O, int K, void* stream) {
     if (M <= 0 || O <= 0 || K <= 0) return GF_ERR_SHAPE;
     if (K > 8) return GF_ERR_UNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     const size_t total = (size_t)M * O;
     const int nb = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
 #define GF_SFW(K_) case K_: small_fwd_kernel<K_><<<dim3(nb), dim3(256), 0, st>>>(x, w, y, total, O); break;
@@ -234,7 +232,7 @@ extern "C" int gf_small_fwd(const float* x, const float* w, float* y, int M, int
         default: small_fwd_kernel<8><<<dim3(nb), dim3(256), 0, st>>>(x, w, y, total, O); break;
     }
 #undef GF_SFW
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -324,7 +322,7 @@ extern "C" int gf_adam_entry_bytes(void) { return (int)sizeof(AdamEntry); }
 extern "C" int gf_multi_adam(const void* table, int n_entries, const float* lr, float* step, const float* found_inf,
                              const float* grad_scale, double beta1, double beta2, float eps, float weight_decay, void* stream) {
     if (n_entries <= 0) return GF_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = gf_stream(stream);
     const AdamEntry* src = static_cast<const AdamEntry*>(table);
     for (int i0 = 0; i0 < n_entries; i0 += ADAM_MAXT) {
         AdamTable tab;
@@ -339,5 +337,5 @@ extern "C" int gf_multi_adam(const void* table, int n_entries, const float* lr, 
         multi_adam_kernel<<<dim3(blocks), dim3(256), 0, st>>>(tab, n, lr, step, found_inf, grad_scale, beta1, beta2, eps, weight_decay);
     }
     adam_step_kernel<<<dim3(1), dim3(1), 0, st>>>(step, found_inf);          // (after every block read the old count: stream order)
-    return (int)hipGetLastError();
+    return gf_launched();
 }

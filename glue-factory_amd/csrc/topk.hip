@@ -13,8 +13,7 @@
 //      deterministic) of the selected entries into LDS;
 //   3. bitonic sort of the <= 4096 survivors by (score descending, list position ascending);
 //   4. scores and the int64 payload (the flat pixel index of the candidate) written in that order.
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 namespace {
 
@@ -152,6 +151,6 @@ extern "C" int gf_topk_candidates(const float* scores, const int* payload, float
     int K2 = 1;
     while (K2 < K) K2 <<= 1;
     topk_candidates_kernel<<<dim3(B), dim3(TK_THREADS), (size_t)K2 * sizeof(unsigned long long),
-                             reinterpret_cast<hipStream_t>(stream)>>>(scores, payload, out_scores, out_payload, n, K, K2);
-    return (int)hipGetLastError();
+                             gf_stream(stream)>>>(scores, payload, out_scores, out_payload, n, K, K2);
+    return gf_launched();
 }

@@ -23,8 +23,7 @@
 // divides by the count; the thread that owns a cluster's root does exactly that.
 //
 // No contraction in this file: torch computes sqrt(dx*dx + dy*dy) and numpy dx*dx + dy*dy with separately rounded products.
-#include "gf_common.h"
-#include "gf_amd.h"
+#include "gf_launch.h"
 
 #pragma clang fp contract(off)
 
@@ -268,9 +267,9 @@ extern "C" int gf_wf_cluster(const float* lines, const float* line_scores, const
     const double eps2 = eps * eps;
     const float lo2 = (float)(eps2 * (1.0 - 1e-5)), hi2 = (float)(eps2 * (1.0 + 1e-5));
     const size_t lds = (size_t)(3 * n + (n > WF_THREADS ? n : WF_THREADS)) * 4;
-    wf_cluster_kernel<<<dim3(B), WF_THREADS, lds, reinterpret_cast<hipStream_t>(stream)>>>(
+    wf_cluster_kernel<<<dim3(B), WF_THREADS, lds, gf_stream(stream)>>>(
         lines, line_scores, fill, junc_idx, num_junctions, out_lines, points, scores, n, P, eps2, lo2, hi2, merge);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_wf_suppress(const float* kpts, const float* kscores, const float* ends, const float* fill, uint8_t* flag,
@@ -278,9 +277,9 @@ extern "C" int gf_wf_suppress(const float* kpts, const float* kscores, const flo
     if (B <= 0 || N <= 0 || P <= 0) return GF_ERR_UNSUPPORTED;
     if (n < 0 || J < 0 || J + N > P) return GF_ERR_SHAPE;
     if (B > 65535) return GF_ERR_UNSUPPORTED;
-    wf_suppress_kernel<<<dim3((N + 255) / 256, B), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    wf_suppress_kernel<<<dim3((N + 255) / 256, B), 256, 0, gf_stream(stream)>>>(
         kpts, kscores, ends, fill, flag, points, scores, N, n, P, J, radius);
-    return (int)hipGetLastError();
+    return gf_launched();
 }
 
 extern "C" int gf_wf_descriptors(const void* map, const float* points, const float* kdesc, const uint8_t* flag, float* out,
@@ -288,29 +287,25 @@ extern "C" int gf_wf_descriptors(const void* map, const float* points, const flo
     if (B <= 0 || P <= 0 || h <= 0 || w <= 0 || C <= 0 || stride <= 0) return GF_ERR_UNSUPPORTED;
     if (J < 0 || J > P) return GF_ERR_SHAPE;
     if (C % 64 || C > 512) return GF_ERR_ALIGN;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)B * P;
     if ((total + 3) / 4 > 0x7fffffff) return GF_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)((total + 3) / 4));
-    if (dtype == GF_BF16)
-        wf_desc_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)map, points, kdesc, flag, out, total, P, J, h, w, C, (float)stride);
-    else if (dtype == GF_F32)
-        wf_desc_kernel<float><<<grid, 256, 0, st>>>((const float*)map, points, kdesc, flag, out, total, P, J, h, w, C, (float)stride);
-    else
-        return GF_ERR_DTYPE;
-    return (int)hipGetLastError();
+    return gf_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        wf_desc_kernel<T><<<grid, 256, 0, gf_stream(stream)>>>((const T*)map, points, kdesc, flag, out, total, P, J, h, w, C, (float)stride);
+        return gf_launched();
+    });
 }
 
 extern "C" int gf_wf_associativity(const int64_t* junc_idx, uint8_t* out, int B, int L, int P, void* stream) {
     if (B <= 0 || L <= 0 || P <= 0) return GF_ERR_UNSUPPORTED;
     if (B > 65535) return GF_ERR_UNSUPPORTED;
-    if (reinterpret_cast<size_t>(out) & 15) return GF_ERR_ALIGN;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (!gf_aligned16(out)) return GF_ERR_ALIGN;
+    hipStream_t st = gf_stream(stream);
     const int64_t total = (int64_t)B * P * P;
     const int64_t want = (total / 16 + 255) / 256;
     wf_zero_kernel<<<dim3((unsigned)(want < 1 ? 1 : want > 8192 ? 8192 : want)), 256, 0, st>>>(out, total);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (int e = gf_launched()) return e;
     wf_assoc_kernel<<<dim3((P + L + 255) / 256, B), 256, 0, st>>>(junc_idx, out, L, P);
-    return (int)hipGetLastError();
+    return gf_launched();
 }

@@ -317,3 +317,76 @@ def test_linear_dw_workspace_matches_recorded():
     slices = lambda m, n, k: (want[f"{m},{n},{k}"] - 256) // (4 * (n * k + n))
     assert slices(255, 256, 256) == 1 and slices(257, 256, 256) == 2 and slices(2049, 1024, 1024) == 7
     assert slices(131072, 1024, 1024) == 8 == slices(131072, 1280, 1024) and slices(131072, 256, 256) == 128
+
+
+def _unknown_dtype_calls(L, lib):
+    """One call per dtype-taking entry point: valid small shapes, null data pointers, dtype code 7."""
+    N, DT = None, 7
+    s = lib.strides(4096, 64, 64)               # [B, 64 tokens, 1 head, 64] in elements: batch, token, head
+    g = lib.strides(64, 8, 1)                   # [batch, 8, 8] row-major
+    plan_out = lib.strides(*([0] * 11))         # gf_gemm_plan's result array (it rejects a null one first)
+    return {
+        "gf_attn_fwd": lambda: L.gf_attn_fwd(N, N, N, N, N, 1, 1, 64, 64, 64, s, s, s, s, 1.0, DT, N),
+        "gf_attn_fwd_ex": lambda: L.gf_attn_fwd_ex(N, N, N, N, N, 1, 1, 64, 64, 64, s, s, s, s, 1.0, DT, 0, N, N),
+        "gf_attn_bwd": lambda: L.gf_attn_bwd(N, N, N, N, N, N, N, N, N, N, 1, 1, 64, 64, 64, s, s, s, s, s, s, s, s, 1.0, DT, N),
+        "gf_attn_bwd_acc": lambda: L.gf_attn_bwd_acc(N, N, N, N, N, N, N, N, N, N, 1, 1, 64, 64, 64, s, s, s, s, s, s, s, s, 1.0,
+                                                     DT, 0, N),
+        "gf_rows_lse": lambda: L.gf_rows_lse(N, N, N, N, 1, 8, 8, 64, DT, N),
+        "gf_rows_argmax": lambda: L.gf_rows_argmax(N, N, N, 1.0, N, N, 1, 8, 8, 64, DT, N),
+        "gf_assign_write": lambda: L.gf_assign_write(N, N, N, N, N, N, 1.0, 0.0, N, N, 1, 8, 8, 64, DT, N),
+        "gf_dual_softmax_bwd": lambda: L.gf_dual_softmax_bwd(N, N, N, N, N, N, N, 8, 1.0, N, 1, 8, 8, 64, DT, N),
+        "gf_line_gather": lambda: L.gf_line_gather(N, N, N, N, 1, 8, 8, 64, DT, N),
+        "gf_line_segsum": lambda: L.gf_line_segsum(N, 64, N, 0, N, N, N, N, 1, 8, 8, 64, 0, DT, N),
+        "gf_line_expand": lambda: L.gf_line_expand(N, N, N, N, 1, 8, 8, 64, 0, DT, N),
+        "gf_rows_gather": lambda: L.gf_rows_gather(N, N, N, 1, 8, 8, 64, DT, N),
+        "gf_multi_cast_transpose": lambda: L.gf_multi_cast_transpose(N, 1, 1, DT, N),
+        "gf_bgemm": lambda: L.gf_bgemm(N, N, N, 1, 8, 8, 8, g, g, g, 1.0, DT, N),
+        "gf_gemm": lambda: L.gf_gemm(N, N, N, N, N, N, N, 0, 64, 32, 32, 0, 32, 0, 32, 0, 32, DT, N),
+        "gf_gemm_plan": lambda: L.gf_gemm_plan(64, 32, 32, 0, 0, 0, 0, 0, DT, plan_out),
+        "gf_linear_dw": lambda: L.gf_linear_dw(N, N, N, N, N, 64, 8, 8, DT, N),
+        "gf_bn_stats": lambda: L.gf_bn_stats(N, N, 8, 8, DT, N),
+        "gf_bn_act_fwd": lambda: L.gf_bn_act_fwd(N, N, N, N, N, N, 8, 8, 0, DT, N),
+        "gf_bn_bwd_stats": lambda: L.gf_bn_bwd_stats(N, N, N, N, N, N, N, 8, 8, 0, DT, N),
+        "gf_bn_bwd_dx": lambda: L.gf_bn_bwd_dx(N, N, N, N, N, N, N, N, N, 8, 8, 0, DT, N),
+        "gf_wf_descriptors": lambda: L.gf_wf_descriptors(N, N, N, N, N, 1, 8, 0, 4, 4, 64, 8, DT, N),
+        "gf_bias_act_bn_nhwc": lambda: L.gf_bias_act_bn_nhwc(N, N, N, N, N, 1, 8, 8, 64, 0, 0, DT, N),
+        "gf_conv1_bias_act_bn": lambda: L.gf_conv1_bias_act_bn(N, N, N, N, N, N, 1, 8, 8, 64, 0, DT, N),
+        "gf_conv3x3_c64": lambda: L.gf_conv3x3_c64(N, N, N, N, N, N, 1, 8, 8, 0, 0, DT, N),
+        "gf_conv3x3_c64_ld": lambda: L.gf_conv3x3_c64_ld(N, N, N, N, N, N, 64, 1, 8, 8, 0, 0, DT, N),
+        "gf_detector_scores": lambda: L.gf_detector_scores(N, N, N, N, N, 1, 4, 4, 0, DT, N),
+        "gf_sample_descriptors": lambda: L.gf_sample_descriptors(N, N, N, 1, 8, 4, 4, 64, 8, DT, N),
+        "gf_rowdot_fwd": lambda: L.gf_rowdot_fwd(N, N, 0.0, N, N, 8, 8, DT, N),
+        "gf_rowdot_bwd": lambda: L.gf_rowdot_bwd(N, N, N, N, N, N, 8, 8, DT, N),
+        "gf_rowdot2_fwd": lambda: L.gf_rowdot2_fwd(N, N, N, N, N, N, N, 8, 8, DT, N),
+        "gf_rowdot2_bwd": lambda: L.gf_rowdot2_bwd(N, N, N, N, N, N, N, 8, 8, DT, N),
+        "gf_lg_loss_fwd": lambda: L.gf_lg_loss_fwd(N, N, N, N, N, N, N, N, N, 0, N, N, N, N, N, N, N, N, N, N, N, N, N,
+                                                   1, 8, 8, 64, DT, N),
+        "gf_lg_loss_bwd_rows": lambda: L.gf_lg_loss_bwd_rows(N, N, N, N, N, 1, N, N, N, 1, 8, 8, 64, DT, N),   # P = 0 returns 0 first
+        "gf_rotary_qk": lambda: L.gf_rotary_qk(N, N, 1, 8, 4, 64, 0, DT, N),
+        "gf_rotary_qk_bwd": lambda: L.gf_rotary_qk_bwd(N, N, N, N, N, 1, 8, 4, 64, DT, N),
+        "gf_ln_gelu_fwd": lambda: L.gf_ln_gelu_fwd(N, N, N, N, N, N, 8, 256, 1e-5, DT, N),
+        "gf_ln_gelu_bwd": lambda: L.gf_ln_gelu_bwd(N, N, N, N, N, N, N, N, N, 8, 256, DT, N),
+    }
+
+
+def test_unknown_dtype_code_is_rejected_before_any_launch():
+    """Every entry point that takes a dtype answers GF_ERR_DTYPE (-4) for a code that is neither fp32 (0) nor bf16 (1), with
+    otherwise valid arguments and before it touches a pointer or the device (csrc/gf_launch.h: gf_by_dtype).
+    Not in the table, because null pointers cannot pass their earlier checks: gf_rows_lse_argmax, gf_rows_top2 and gf_hv_warp
+    (GF_ERR_SHAPE for a null output / input) and gf_linear_dw2 (GF_ERR_UNSUPPORTED for a null source).  The bf16-only entry
+    points answer GF_ERR_UNSUPPORTED (-1) for every other code, fp32 included, in one test with the head_dim: pinned below."""
+    from glue_factory_amd import lib
+    L = lib.load()
+    calls = _unknown_dtype_calls(L, lib)
+    got = {name: call() for name, call in calls.items()}
+    assert got == {name: -4 for name in calls}
+    # every dtype-taking declaration is either in the table or named above
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gf_amd.h")).read(), flags=re.S)
+    takes_dtype = {m.group(1) for m in re.finditer(r"\b(gf_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", text) if "dtype" in m.group(2)}
+    bf16_only = {"gf_attn_cross_bwd", "gf_head_bwd", "gf_gemm_res2"}
+    left_out = {"gf_rows_lse_argmax", "gf_rows_top2", "gf_hv_warp", "gf_linear_dw2"}
+    assert takes_dtype == set(calls) | bf16_only | left_out
+    N, s = None, lib.strides(4096, 64, 64)
+    assert L.gf_attn_cross_bwd(N, N, N, N, N, N, N, N, 2, 1, 1, 64, 64, s, s, s, s, s, s, 1.0, 7, N) == -1
+    assert L.gf_head_bwd(N, N, N, N, N, N, N, N, 1, 8, 8, 256, 7, N) == -1
+    assert L.gf_gemm_res2(N, N, N, N, N, N, N, 64, 256, 256, 0, 256, 0, 256, 256, 256, 256, 7, N) == -1
