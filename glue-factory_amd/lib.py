@@ -123,6 +123,10 @@ SIGNATURES = {
     "gf_ln_gelu_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _P],
     "gf_ln_gelu_nblk": [_I],
     "gf_ln_gelu_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "gf_ak_deform_cols": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "gf_ak_aggregate": [_P] * 8 + [_I] * 9 + [_P],
+    "gf_ak_dkd_refine": [_P] * 5 + [_I] * 5 + [_F, _P],
+    "gf_ak_sddh": [_P] * 9 + [_I] * 7 + [_P],
 }
 _RESTYPE = {"gf_h_ws_bytes": _c.c_int64, "gf_hl_ws_bytes": _c.c_int64, "gf_e_ws_bytes": _c.c_int64, "gf_sinkhorn_ws_bytes": _c.c_int64, "gf_linear_dw_ws_bytes": _c.c_int64}
 

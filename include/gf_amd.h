@@ -812,6 +812,41 @@ int gf_ln_gelu_bwd(const void* x, const float* gamma, const float* beta, const f
                    const float* rstd, const void* dy, void* dx, float* dgamma_part,
                    float* dbeta_part, int R, int C, int dtype, void* stream);
 
+/* ---- frozen ALIKED extractor (gluefactory/models/extractors/aliked.py; csrc/aliked.hip) ------------------------
+ * fp32 only, no gradient.  Every entry: a null pointer or a non-positive size -> GF_ERR_SHAPE.
+ * gf_ak_deform_cols: column matrix of a 3 x 3 deformable convolution (:270-328; the sampling rule of the published
+ *   deform_conv2d, groups 1, stride 1, dilation 1, no mask).  x [B,C,H,W], offset [B,18,H,W] (already clamped),
+ *   cols [B, C*9, H*W] with row c*9 + k, k = ky*3 + kx: the bilinear value at (y - pad + ky + offset[2k],
+ *   x - pad + kx + offset[2k+1]); 0 at py <= -1, py >= H, px <= -1, px >= W; a corner outside the map counts 0.
+ *   H * W >= 2^24 -> GF_ERR_UNSUPPORTED.
+ * gf_ak_aggregate: feature aggregation + normalisation + first layer of the score head in one pass (:749-759).
+ *   x1 [B,c1,Hp,Wp]; g2, g3, g4 [B,dim/4,Hp/2^s,Wp/2^s] for s = 1, 3, 5 (already gated); w1 [dim/4, c1] = conv1.weight;
+ *   w8 [8, dim] = score_head.0.weight.  Per pixel: x1234 = (selu(w1 x1), up(g2), up(g3), up(g4)) with the
+ *   align_corners=True bilinear rule; feat [B,H,W,dim] channels-last = x1234 / max(|x1234|, 1e-12) for the crop
+ *   rows top..top+H, columns left..left+W only; s8 [B,8,Hp,Wp] = selu(w8 x1234) at padded size.
+ *   (c1, dim) in {(8, 64), (16, 128)}, else GF_ERR_UNSUPPORTED; Hp, Wp multiples of 32 holding the crop, else GF_ERR_SHAPE;
+ *   feat 16-byte aligned.
+ * gf_ak_dkd_refine: DKD's sub-pixel step for selected pixels (:165-216).  score [B,H,W], idx [B,N] flat pixel indices;
+ *   kxy [B,N,2] = (pixel + soft-argmax residual over the (2r+1)^2 window, zeros outside the map, temperature T)
+ *   / (W-1, H-1) * 2 - 1; disp [B,N] the score dispersity; kscore [B,N] the bilinear score at kxy
+ *   (grid_sample, align_corners=True, zero padding).  radius 1..4 (the window lives in registers), else
+ *   GF_ERR_UNSUPPORTED; H, W >= 2; N == 0 is a no-op.
+ * gf_ak_sddh: the descriptor head (:513-588) for pos [B,N,2] = keypoints in PIXELS of the map (the caller computes
+ *   (k / 2 + 0.5) (W-1, H-1) in the reference's order; the kernel truncates it).  feat [B,H,W,dim] channels-last;
+ *   w1 [2M][K*K][dim] = offset_conv.0.weight with the channel last, b1 [2M]; w2 [2M][2M], b2 [2M] = offset_conv.2;
+ *   sf [dim][dim] = sf_conv.weight; aggT [M][d][c] = agg_weights transposed in its last two axes; out [B,N,dim],
+ *   L2-normalised.  dim in {64, 128}, M in {16, 32}, K in {1, 3}, else GF_ERR_UNSUPPORTED; H, W >= K + 1;
+ *   feat, w1, sf, aggT, out 16-byte aligned (GF_ERR_ALIGN); N == 0 is a no-op. */
+int gf_ak_deform_cols(const float* x, const float* offset, float* cols, int B, int C, int H, int W, int pad, void* stream);
+int gf_ak_aggregate(const float* x1, const float* g2, const float* g3, const float* g4, const float* w1, const float* w8,
+                    float* feat, float* s8, int B, int c1, int dim, int Hp, int Wp, int top, int left, int H, int W,
+                    void* stream);
+int gf_ak_dkd_refine(const float* score, const int64_t* idx, float* kxy, float* kscore, float* disp, int B, int N, int H,
+                     int W, int radius, float temperature, void* stream);
+int gf_ak_sddh(const float* feat, const float* pos, const float* w1, const float* b1, const float* w2, const float* b2,
+               const float* sf, const float* aggT, float* out, int B, int N, int H, int W, int dim, int M, int K,
+               void* stream);
+
 #ifdef __cplusplus
 }
 #endif
