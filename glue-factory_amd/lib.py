@@ -127,8 +127,14 @@ SIGNATURES = {
     "gf_ak_aggregate": [_P] * 8 + [_I] * 9 + [_P],
     "gf_ak_dkd_refine": [_P] * 5 + [_I] * 5 + [_F, _P],
     "gf_ak_sddh": [_P] * 9 + [_I] * 7 + [_P],
+    "gf_sift_blur": [_P] * 4 + [_I] * 5 + [_L] * 3 + [_I, _D, _P],
+    "gf_sift_extrema_ws_ints": [_I, _I, _I],
+    "gf_sift_extrema": [_P, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _I, _P],
+    "gf_sift_orient": [_P, _P, _I] + [_P] * 7 + [_I, _I, _P],
+    "gf_sift_describe": [_P, _P, _I] + [_P] * 7 + [_I, _I, _I, _P],
+    "gf_sift_dedupe": [_P] * 8 + [_I] * 4 + [_P],
 }
-_RESTYPE = {"gf_h_ws_bytes": _c.c_int64, "gf_hl_ws_bytes": _c.c_int64, "gf_e_ws_bytes": _c.c_int64, "gf_sinkhorn_ws_bytes": _c.c_int64, "gf_linear_dw_ws_bytes": _c.c_int64}
+_RESTYPE = {"gf_sift_extrema_ws_ints": _c.c_int64, "gf_h_ws_bytes": _c.c_int64, "gf_hl_ws_bytes": _c.c_int64, "gf_e_ws_bytes": _c.c_int64, "gf_sinkhorn_ws_bytes": _c.c_int64, "gf_linear_dw_ws_bytes": _c.c_int64}
 
 _lib = None
 

@@ -847,6 +847,45 @@ int gf_ak_sddh(const float* feat, const float* pos, const float* w1, const float
                const float* sf, const float* aggT, float* out, int B, int N, int H, int W, int dim, int M, int K,
                void* stream);
 
+/* ---- SIFT extractor (glue_factory_amd/extractors/sift.py states the semantics; csrc/sift.hip) ------------------
+ * fp32 only, no gradient.  Every entry: a null pointer it needs or a non-positive size -> GF_ERR_SHAPE.
+ * gf_sift_blur: one Gaussian level.  dst [B][H,W] = the source blurred by `sigma` (separable normalised kernel, radius
+ *   ceil(4 sigma), reflect-101 borders); the source is src [B][Hs,Ws] read directly (mode 0, H == Hs, W == Ws), through
+ *   2x bilinear upsampling with align_corners=False (mode 1, H == 2 Hs, W == 2 Ws, dog must be NULL) or at every second
+ *   pixel (mode 2, H == (Hs + 1) / 2, W == (Ws + 1) / 2).  dog (may be NULL) [B][H,W] = dst - source; src_copy (may be
+ *   NULL) [B][H,W] = the source on the output grid (an octave's level 0).  Image b starts at b * src_bstride /
+ *   out_bstride (dst and src_copy) / dog_bstride elements.  H, W, Hs, Ws >= 2; radius > 16 -> GF_ERR_UNSUPPORTED.
+ * gf_sift_extrema: candidates of ONE octave's DoG stack dog [B,5,H,W]: strict 26-neighbour extrema of levels 1..3 with
+ *   |D| > 0.8 thr, refined (<= 5 steps), kept when |D^| >= thr, det > 0 and tr^2 r < (r + 1)^2 det.  Appends to per-image
+ *   lists meta [B,cap,4] int32 (octave, layer, y, x of the refined cell) and vals [B,cap,4] (offsets x, y, s, D^) at
+ *   slot count[b]..., in ascending order of the cell where the extremum was FOUND (layer, y, x), equal bit for bit across
+ *   calls; count [B] (the caller zeroes it before the first octave) keeps counting past cap, slots >= cap are not
+ *   written.  ws: gf_sift_extrema_ws_ints(B, H, W) int32 of scratch.  H, W >= 3; 5 H W >= 2^31 -> GF_ERR_UNSUPPORTED.
+ * gf_sift_orient / gf_sift_describe: one wave per keypoint.  levels[o] -> octave o's Gaussian levels [B,6,h,w]
+ *   (contiguous), hw[2 o], hw[2 o + 1] = h, w (HOST arrays, noct <= 8 entries).  Per keypoint [B,N]: oct (outside
+ *   0..noct-1 -> the keypoint is skipped: valid 0 / a zero descriptor), lvl (clamped to 0..5), sigma in octave pixels
+ *   (outside (0, 16] -> skipped).  orient: integer cell xi, yi -> ori [B,N,2] in [0, 2 pi), strongest first, valid
+ *   [B,N,2] int32.  describe: refined position xo, yo (octave pixels) and ori [B,N] -> desc [B,N,128] (8-byte aligned, else
+ *   GF_ERR_ALIGN): L2, clip 0.2, L2, then sift_to_rootsift when rootsift != 0.  Pixels closer than 1 px to the border
+ *   do not contribute.  N == 0 is a no-op.
+ * gf_sift_dedupe: the first two steps of filter_dog_point on pixels ix, iy [B,N] int32: per pixel of [B,H,W] the highest
+ *   score (>= 0), then the lowest |angle|; keep [B,N] int32 marks every entry that attains both (ties all stay); entries
+ *   with valid == 0, a negative score or a pixel outside the map are never kept.  buf [B,H,W] uint64 scratch (8-byte
+ *   aligned) and sbuf [B,H,W] (the kept score per pixel, 0 elsewhere: the input of the max-pool NMS) are cleared by the
+ *   call. */
+int gf_sift_blur(const float* src, float* dst, float* dog, float* src_copy, int B, int Hs, int Ws, int H, int W,
+                 int64_t src_bstride, int64_t out_bstride, int64_t dog_bstride, int mode, double sigma, void* stream);
+int64_t gf_sift_extrema_ws_ints(int B, int H, int W);
+int gf_sift_extrema(const float* dog, int B, int H, int W, int octave, double thr, double edge_r, int* ws, int* count, int* meta,
+                    float* vals, int cap, void* stream);
+int gf_sift_orient(const void* const* levels, const int* hw, int noct, const int* oct, const int* lvl, const int* xi,
+                   const int* yi, const float* sigma, float* ori, int* valid, int B, int N, void* stream);
+int gf_sift_describe(const void* const* levels, const int* hw, int noct, const int* oct, const int* lvl, const float* xo,
+                     const float* yo, const float* sigma, const float* ori, float* desc, int B, int N, int rootsift,
+                     void* stream);
+int gf_sift_dedupe(const int* ix, const int* iy, const float* score, const float* angle, const int* valid, void* buf, float* sbuf,
+                   int* keep, int B, int N, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
